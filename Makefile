@@ -15,7 +15,7 @@ test-gpu:
 	$(PYTHON) -m pytest tests -q -m gpu
 
 bench:
-	$(PYTHON) bench.py --gpus 1 --steps 10 --warmup 3
+	$(PYTHON) bench.py --gpus 1 --steps 10 --warmup 3 --full
 
 bench-micro:
 	$(PYTHON) scripts/bench_micro.py

@@ -19,7 +19,15 @@ Setup (untimed) populates the index through the real write path
 ingest rate as config.ingest_blocks_per_sec.
 
 Usage (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: setup, warmup, the
+K timed steps, the optional output dump, the result line.  --full adds
+the secondary measurements (single-prompt latency, wire/gRPC service
+QPS, same-harness CPU baseline proxy -> vs_baseline); without it those
+fields are null.  --dump-outputs DIR writes what the last timed step
+computed (per-prompt score rows and top pods of its last
+--distinct-calls calls) as DIR/<name>.npy; inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 N>1 is launched by the driver via torch.distributed.run (one rank per
 GPU over RCCL). Default multi-GPU mode REPLICATES the index (it fits in
 one MI355X's HBM by orders of magnitude) and gives each rank its own
@@ -486,6 +494,44 @@ def measure_cpu_proxy(capacity, prefix_frac):
     return n * B / (time.monotonic() - t0)
 
 
+DUMP_SCORE_BYTES = 48 << 20  # score rows kept by --dump-outputs (fp32)
+
+
+def dump_outputs(out_dir, last_out):
+    """Writes what the last timed step's calls returned: for each staged
+    prompt batch (slot) the [prompts, pods] fp32 score matrix and the
+    top pod per prompt of the most recent call on it.  Files:
+      scores.npy   float32 [slots, rows, pods]
+      top_pod.npy  float64 [slots, rows]   (pod ids, exact in float64)
+      rows.npy     float64 [rows]          prompt index of each kept row
+      slots.npy    float64 [slots]         staged-batch index of each slot
+    When the score matrices exceed DUMP_SCORE_BYTES the same seeded
+    sample of prompt rows is kept from every slot."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    slots = sorted(last_out)
+    n_rows, n_pods = last_out[slots[0]][0].shape
+    keep = DUMP_SCORE_BYTES // (len(slots) * max(n_pods, 1) * 4)
+    if keep < n_rows:
+        rows = np.sort(np.random.default_rng(2024).choice(
+            n_rows, size=max(keep, 1), replace=False))
+    else:
+        rows = np.arange(n_rows)
+    rows_t = torch.from_numpy(rows)
+    scores = np.stack([
+        last_out[s][0].index_select(
+            0, rows_t.to(last_out[s][0].device)).float().cpu().numpy()
+        for s in slots])
+    top = np.stack([last_out[s][1].cpu().numpy()[rows] for s in slots])
+    np.save(os.path.join(out_dir, "scores.npy"),
+            scores.astype(np.float32, copy=False))
+    np.save(os.path.join(out_dir, "top_pod.npy"), top.astype(np.float64))
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "slots.npy"),
+            np.asarray(slots, dtype=np.float64))
+
+
 def main():
     global NUM_BLOCKS, NUM_PODS
     ap = argparse.ArgumentParser()
@@ -520,12 +566,23 @@ def main():
                          "shared prefix (hit ratio of the workload)")
     ap.add_argument("--graph", action="store_true",
                     help="capture the read call in a hipGraph and replay")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the "
+                         "timed steps: single-prompt latency, wire/gRPC "
+                         "service QPS and the same-harness CPU baseline "
+                         "proxy (vs_baseline); off by default, those "
+                         "fields are then null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step "
+                         "computed as DIR/<name>.npy (float32/float64, "
+                         "<= 64 MB in all; larger outputs are cut to a "
+                         "fixed seeded sample of prompts)")
     ap.add_argument("--no-wire", action="store_true",
-                    help="skip the wire-level service benchmark (real "
-                         "sockets against the native front)")
+                    help="with --full: skip the wire-level service "
+                         "benchmark (real sockets against the native front)")
     ap.add_argument("--no-baseline-proxy", action="store_true",
-                    help="skip the inline same-harness CPU baseline "
-                         "measurement (vs_baseline becomes null)")
+                    help="with --full: skip the inline same-harness CPU "
+                         "baseline measurement (vs_baseline stays null)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="use the ShardedIndex/RCCL path even at world=1 "
                          "(single-GPU validation of the collective path)")
@@ -650,7 +707,12 @@ def main():
             BLOCK_SIZE, KEYS_PER_PROMPT, 0, 1)  # row_major: no transpose
         return hashes_t.view(-1)
 
-    def probe_score(hashes):
+    # what the most recent call on each staged batch returned to its
+    # caller (references only - read after the timed region by
+    # --dump-outputs)
+    last_out = {}
+
+    def probe_score(hashes, slot):
         if sharded is not None:
             scores = sharded.sharded_scores(hashes, key_offsets, MODEL,
                                             set(), weights)
@@ -663,7 +725,9 @@ def main():
             scores = index.fused_scores(hashes, key_offsets, MODEL, set(),
                                         weights, max_k=KEYS_PER_PROMPT)
         best = scores.argmax(dim=1)
-        return best.cpu(), scores[:, 0].sum().item()  # forces D2H
+        best_host = best.cpu()  # forces D2H
+        last_out[slot] = (scores, best_host)
+        return best_host, scores[:, 0].sum().item()
 
     def score_call_cpu(call_idx):
         call_idx = call_idx % distinct
@@ -685,6 +749,7 @@ def main():
                 no_filter.cpu(), weights, num_pods,
                 index.table.next_epoch())
         best = scores.argmax(dim=1)
+        last_out[call_idx] = (scores, best)
         return best, float(scores[:, 0].sum())
 
     graph = None
@@ -705,7 +770,7 @@ def main():
                 *index.table._t(), hashes, key_offsets, model_id,
                 no_filter, weights, num_pods, frozen_epoch_note,
                 KEYS_PER_PROMPT, n_tiers)
-            return scores.argmax(dim=1)
+            return scores, scores.argmax(dim=1)
 
         try:
             static_tok.copy_(call_tokens[0])
@@ -717,7 +782,7 @@ def main():
             torch.cuda.current_stream().wait_stream(warm)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_best = graph_body()
+                static_scores, static_best = graph_body()
             torch.cuda.synchronize()
             log(rank, "# hipGraph capture OK")
         except Exception as e:  # pragma: no cover - graph support varies
@@ -730,8 +795,12 @@ def main():
         for c in range(args.calls_per_step):
             static_tok.copy_(call_tokens[c % len(call_tokens)])
             graph.replay()
-            static_best.cpu()
+            best_host = static_best.cpu()
             torch.cuda.synchronize()
+            # the next replay overwrites static_scores, so only the
+            # most recent call's output stays readable
+            last_out.clear()
+            last_out[c % len(call_tokens)] = (static_scores, best_host)
             t1 = time.monotonic()
             lat.append(t1 - t0)
             t0 = t1
@@ -741,7 +810,7 @@ def main():
     # side stream overlapped with the current call's probe+score+D2H, and
     # the pipeline CARRIES ACROSS STEPS - only the very first call of a
     # run pays an unoverlapped chain.
-    pipe = {"hashes": None}
+    pipe = {"hashes": None, "slot": 0}
 
     def one_step():
         if graph is not None:
@@ -763,9 +832,10 @@ def main():
                 next_hashes = chain_call(c + 1)
             ev = torch.cuda.Event()
             ev.record(chain_stream)
-            probe_score(hashes)
+            probe_score(hashes, pipe["slot"])
             torch.cuda.current_stream().wait_event(ev)
             pipe["hashes"] = next_hashes
+            pipe["slot"] = (c + 1) % len(call_tokens)
             torch.cuda.synchronize()
             t1 = time.monotonic()
             lat.append(t1 - t0)
@@ -805,6 +875,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out)
+
+    # Everything from here to the result line is secondary and runs only
+    # with --full.
     # single-prompt request latency (separate, not part of the headline):
     # one 8k-token prompt through the PRODUCTION single-prompt route -
     # host-side chain (C++ FNV + session chain cache, token_processor.py)
@@ -817,7 +892,7 @@ def main():
     # every call, full CPU chain + cache store).
     single_ms = None
     single_cold_ms = None
-    if index.table.is_cuda and sharded is None:
+    if args.full and index.table.is_cuda and sharded is None:
         import numpy as np
 
         tp1 = ChunkedTokenDatabase(TokenProcessorConfig(
@@ -868,8 +943,8 @@ def main():
     # (tokenization subsystem included), wire_qps_tokens the
     # pre-tokenized hot API.
     wire_stats = None
-    if (use_gpu and rank == 0 and sharded is None and world == 1
-            and not args.no_wire):
+    if (args.full and use_gpu and rank == 0 and sharded is None
+            and world == 1 and not args.no_wire):
         try:
             wire_indexer = build_wire_indexer(index)
             wire_stats = measure_wire(wire_indexer, chains,
@@ -891,7 +966,7 @@ def main():
     # the Go code (contiguous open addressing, no GC, no LRU locks), so
     # vs_baseline is conservative.
     proxy_qps = None
-    if (use_gpu and rank == 0 and sharded is None
+    if (args.full and use_gpu and rank == 0 and sharded is None
             and not args.no_baseline_proxy):
         proxy_qps = measure_cpu_proxy(capacity, args.prefix_frac)
         log(rank, f"# cpu baseline proxy: {proxy_qps:.1f} scores/s")

@@ -65,6 +65,39 @@ class TestBenchContract:
         assert d["config"]["prefix_frac"] == 1.0
         assert d["config"]["num_pods"] == 8
 
+    def test_steps_and_full_flags(self):
+        d = run_bench(["--steps", "3", "--full"])
+        assert d["steps"] == 3
+        assert d["ms_per_step"] > 0
+        # one call of 32 prompts per step: value is prompts over the
+        # timed steps, so it must agree with ms_per_step
+        assert d["value"] == pytest.approx(32 / (d["ms_per_step"] / 1e3),
+                                           rel=1e-2)
+
+    def test_dump_outputs_is_reproducible(self, tmp_path):
+        import numpy as np
+
+        dumps = []
+        for name in ("a", "b"):
+            out = tmp_path / name
+            run_bench(["--dump-outputs", str(out)])
+            dumps.append({f: np.load(out / f) for f in sorted(
+                p.name for p in out.iterdir())})
+        a, b = dumps
+        assert {"scores.npy", "top_pod.npy"} <= set(a)
+        assert set(a) == set(b)
+        for f in a:
+            assert a[f].dtype in (np.float32, np.float64), f
+            assert np.array_equal(a[f], b[f]), f
+        scores, top = a["scores.npy"], a["top_pod.npy"]
+        assert scores.shape[1:] == (32, scores.shape[2])
+        assert top.shape == scores.shape[:2]
+        # half of every prompt is an index-resident prefix: every prompt
+        # scores, and the dumped top pod is the argmax of its score row
+        assert (scores.max(axis=2) > 0).all()
+        assert np.array_equal(top, scores.argmax(axis=2))
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+
 
 @pytest.mark.timeout(600)
 class TestBenchTorchrun:

@@ -196,14 +196,29 @@ class TestPool:
 
 
 @pytest.fixture
-def uds_server(tokenizer_fixture_dir, tmp_path):
+def sock_dir():
+    """Short private directory for unix sockets.  sockaddr_un caps the
+    path at 107 bytes and pytest's tmp_path (base temp + user + test
+    name) can exceed that, so sockets get a directory of their own."""
+    import shutil
+    import tempfile
+
+    base = "/tmp" if os.access("/tmp", os.W_OK) else None
+    d = tempfile.mkdtemp(prefix="kvuds-", dir=base)
+    assert len(os.path.join(d, "tok.socket")) < 100, d
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
+def uds_server(tokenizer_fixture_dir, sock_dir):
     """Runs the real aiohttp UDS sidecar in a background thread."""
     import sys
 
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
     from services.uds_tokenizer import server as uds
 
-    sock_path = str(tmp_path / "tok.socket")
+    sock_path = os.path.join(sock_dir, "tok.socket")
     uds.core.reload({"local_dir": tokenizer_fixture_dir})
     app = uds.make_app()
 
@@ -463,7 +478,7 @@ class TestUdsMultiWorker:
         return proc
 
     def test_prefork_serves_and_restarts(self, tokenizer_fixture_dir,
-                                         tmp_path):
+                                         sock_dir):
         import signal
         import subprocess
         import threading
@@ -472,7 +487,7 @@ class TestUdsMultiWorker:
         from llmd_kvcache_amd.tokenization.uds import (UdsTokenizer,
                                                        UdsTokenizerConfig)
 
-        sock_path = str(tmp_path / "mw.socket")
+        sock_path = os.path.join(sock_dir, "mw.socket")
         proc = self._spawn(sock_path, tokenizer_fixture_dir, workers=2)
         try:
             client = UdsTokenizer(UdsTokenizerConfig(
