@@ -20,6 +20,7 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
 from .kvblock.index import Index, IndexConfig, new_index
+from .utils import hashing
 from .utils.logging import get_logger, trace
 from .kvblock.keys import Key
 from .kvblock.token_processor import ChunkedTokenDatabase, TokenProcessorConfig
@@ -180,7 +181,7 @@ class Indexer:
         fused = getattr(self._kv_block_index, "fused_scores", None)
         tp = self.tokens_processor
         native = (fused is not None and tp._native is not None
-                  and tp.config.hash_algo == "fnv-64a")
+                  and tp.config.hash_algo in hashing.NATIVE_ALGO_IDS)
         if not native:
             keys_per_prompt = [
                 tp.tokens_to_kv_block_keys(None, t, model_name)
@@ -229,7 +230,8 @@ class Indexer:
         init = _to_i64(tp.config.init_hash())
         parents = torch.full((B,), init, dtype=torch.int64)
         hashes, chunk_off = idx.table.ops.hash_chain_batch(
-            tokens_flat, offsets, parents, bs)
+            tokens_flat, offsets, parents, bs,
+            hashing.NATIVE_ALGO_IDS[tp.config.hash_algo])
         counts = (chunk_off[1:] - chunk_off[:-1]).to(torch.int32)
         max_k = int(counts.max()) if B else 0
         num_pods = idx._num_pods_padded()

@@ -26,6 +26,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import torch
 
 from ..scorer import default_kv_cache_backend_configs
+from ..utils import hashing
 from .index import Index
 from .keys import Key, PodEntry
 
@@ -585,6 +586,16 @@ class GpuIndex(TableIndex):
             token_processor = ChunkedTokenDatabase()
         block_size = token_processor.block_size
         init_hash = token_processor.config.init_hash()
+        # The kernels compute the request-key chain themselves, so they
+        # must run the token processor's algorithm.  One without a native
+        # id cannot run on-device: raise, and kvevents.Pool falls back to
+        # its per-event Python path.
+        hash_algo = token_processor.config.hash_algo
+        algo_id = hashing.NATIVE_ALGO_IDS.get(hash_algo)
+        if algo_id is None:
+            raise ValueError(
+                f"hash_algo {hash_algo!r} has no native chain kernel; "
+                "apply these events through the per-event path")
 
         import numpy as np
 
@@ -786,21 +797,21 @@ class GpuIndex(TableIndex):
                     *self.table._t(), tok_t, *common[:7],
                     ev_of_t, common[8], _to_i64(init_hash), block_size,
                     self.table.next_epoch(), self.cfg.shard_id,
-                    self.cfg.num_shards, max_tokens,
+                    self.cfg.num_shards, max_tokens, algo_id,
                 )
             else:
                 self.table.ops.gpu_apply_events_split(
                     *self.table._t(), tok_t, *common[:8], ev_of_t,
                     common[8], _to_i64(init_hash), block_size,
                     self.table.next_epoch(), self.cfg.shard_id,
-                    self.cfg.num_shards,
+                    self.cfg.num_shards, algo_id,
                 )
         else:
             self.table.ops.gpu_apply_events(
                 *self.table._t(), tok_t, *common,
                 _to_i64(init_hash), block_size,
                 self.table.next_epoch(), self.cfg.shard_id,
-                self.cfg.num_shards,
+                self.cfg.num_shards, algo_id,
             )
         if up is not None:
             up.end()

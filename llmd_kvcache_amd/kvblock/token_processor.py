@@ -33,8 +33,9 @@ class TokenProcessorConfig:
     # Aligned with vLLM's PYTHONHASHSEED; see token_processor.go:36-40.
     hash_seed: str = ""
     # Pluggable chain hash (utils.hashing.CHAIN_ALGOS): "fnv-64a" is
-    # current vLLM/reference behavior and the only algo with C++/HIP
-    # fast paths; alternatives run on the Python path.
+    # current vLLM/reference behavior.  Every algo listed in
+    # hashing.NATIVE_ALGO_IDS (fnv-64a and the two sha256-cbor-64
+    # variants) has C++/HIP fast paths; any other runs in Python.
     hash_algo: str = "fnv-64a"
     # Host-side session/prefix chain cache (kvblock/chain_cache.py):
     # warm shared prefixes skip the serial FNV/CBOR chain entirely.
@@ -111,9 +112,10 @@ class ChunkedTokenDatabase:
         n_chunks = len(tokens) // bs
         if n_chunks == 0:
             return []
-        if self._native is not None and self.config.hash_algo == "fnv-64a":
+        algo_id = hashing.NATIVE_ALGO_IDS.get(self.config.hash_algo)
+        if self._native is not None and algo_id is not None:
             return self._native.tokens_to_chunk_hashes(
-                list(tokens[: n_chunks * bs]), parent_hash, bs
+                list(tokens[: n_chunks * bs]), parent_hash, bs, algo_id
             )
         link = hashing.CHAIN_ALGOS[self.config.hash_algo][0]
         hashes = []

@@ -9,11 +9,12 @@ namespace kvidx {
 // cpu_ops.cpp
 std::vector<uint64_t> tokens_to_chunk_hashes(std::vector<uint64_t> tokens,
                                              uint64_t parent,
-                                             int64_t block_size);
+                                             int64_t block_size,
+                                             int64_t algo);
 std::vector<at::Tensor> hash_chain_batch(at::Tensor, at::Tensor, at::Tensor,
-                                         int64_t);
+                                         int64_t, int64_t);
 std::vector<uint64_t> tokens_to_chunk_hashes_fast(std::vector<uint64_t>,
-                                                  uint64_t, int64_t);
+                                                  uint64_t, int64_t, int64_t);
 void cpu_insert(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                 at::Tensor, at::Tensor, int64_t, at::Tensor, at::Tensor,
                 int64_t, at::Tensor, int64_t, int64_t, int64_t, int64_t);
@@ -66,27 +67,27 @@ at::Tensor gpu_fused_score(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                            at::Tensor, int64_t, int64_t, int64_t, int64_t);
 at::Tensor gpu_score_from_masks(at::Tensor, at::Tensor, at::Tensor, int64_t);
 std::vector<at::Tensor> gpu_hash_chain(at::Tensor, at::Tensor, at::Tensor,
-                                       int64_t);
+                                       int64_t, int64_t);
 at::Tensor gpu_hash_chain_tr(at::Tensor, at::Tensor, at::Tensor, int64_t,
-                             int64_t, int64_t, int64_t);
+                             int64_t, int64_t, int64_t, int64_t);
 void gpu_apply_events(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, int64_t, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor, int64_t, int64_t, int64_t, int64_t,
-                      int64_t);
+                      int64_t, int64_t);
 void gpu_apply_events_split(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, at::Tensor, int64_t,
                             at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, at::Tensor, int64_t,
-                            int64_t, int64_t, int64_t, int64_t);
+                            int64_t, int64_t, int64_t, int64_t, int64_t);
 void gpu_apply_events_split_tr(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, at::Tensor, int64_t,
                             at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, int64_t, int64_t,
-                            int64_t, int64_t, int64_t, int64_t);
+                            int64_t, int64_t, int64_t, int64_t, int64_t);
 #endif
 
 namespace wire {
@@ -97,9 +98,17 @@ void register_wirefront(pybind11::module_& m);  // wirefront.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native KV-block index ops (CPU reference + gfx950 HIP)";
-  m.def("tokens_to_chunk_hashes", &kvidx::tokens_to_chunk_hashes);
-  m.def("hash_chain_batch", &kvidx::hash_chain_batch);
-  m.def("tokens_to_chunk_hashes_fast", &kvidx::tokens_to_chunk_hashes_fast);
+  // Chain ops take a trailing native algo id (utils/hashing.py
+  // NATIVE_ALGO_IDS); 0 = fnv-64a is the default everywhere.
+  m.def("tokens_to_chunk_hashes", &kvidx::tokens_to_chunk_hashes,
+        py::arg("tokens"), py::arg("parent"), py::arg("block_size"),
+        py::arg("algo") = 0);
+  m.def("hash_chain_batch", &kvidx::hash_chain_batch,
+        py::arg("tokens"), py::arg("offsets"), py::arg("parents"),
+        py::arg("block_size"), py::arg("algo") = 0);
+  m.def("tokens_to_chunk_hashes_fast", &kvidx::tokens_to_chunk_hashes_fast,
+        py::arg("tokens"), py::arg("parent"), py::arg("block_size"),
+        py::arg("algo") = 0);
   m.def("cpu_insert", &kvidx::cpu_insert);
   m.def("cpu_compact", &kvidx::cpu_compact);
   m.def("cpu_evict", &kvidx::cpu_evict);
@@ -116,14 +125,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_lookup", &kvidx::gpu_lookup);
   m.def("gpu_fused_score", &kvidx::gpu_fused_score);
   m.def("gpu_score_from_masks", &kvidx::gpu_score_from_masks);
-  m.def("gpu_hash_chain", &kvidx::gpu_hash_chain);
+  m.def("gpu_hash_chain", &kvidx::gpu_hash_chain,
+        py::arg("tokens"), py::arg("tok_off"), py::arg("parents"),
+        py::arg("block_size"), py::arg("algo") = 0);
   m.def("gpu_hash_chain_tr", &kvidx::gpu_hash_chain_tr,
         py::arg("tokens_t"), py::arg("parents"), py::arg("n_chunks"),
         py::arg("block_size"), py::arg("max_chunks"), py::arg("ilp") = 0,
-        py::arg("row_major") = 0);
-  m.def("gpu_apply_events", &kvidx::gpu_apply_events);
-  m.def("gpu_apply_events_split", &kvidx::gpu_apply_events_split);
-  m.def("gpu_apply_events_split_tr", &kvidx::gpu_apply_events_split_tr);
+        py::arg("row_major") = 0, py::arg("algo") = 0);
+  m.def("gpu_apply_events", &kvidx::gpu_apply_events,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens"), py::arg("tok_off"),
+        py::arg("ehashes"), py::arg("eh_off"), py::arg("parents"),
+        py::arg("has_parent"), py::arg("ev_type"), py::arg("pod_entry"),
+        py::arg("grp_off"), py::arg("model_of"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("epoch"), py::arg("shard_id"),
+        py::arg("num_shards"), py::arg("algo") = 0);
+  m.def("gpu_apply_events_split", &kvidx::gpu_apply_events_split,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens"), py::arg("tok_off"),
+        py::arg("ehashes"), py::arg("eh_off"), py::arg("parents"),
+        py::arg("has_parent"), py::arg("ev_type"), py::arg("pod_entry"),
+        py::arg("grp_off"), py::arg("ev_of"), py::arg("model_of"),
+        py::arg("init_hash_bits"), py::arg("block_size"), py::arg("epoch"),
+        py::arg("shard_id"), py::arg("num_shards"), py::arg("algo") = 0);
+  m.def("gpu_apply_events_split_tr", &kvidx::gpu_apply_events_split_tr,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("tok_off"),
+        py::arg("ehashes"), py::arg("eh_off"), py::arg("parents"),
+        py::arg("has_parent"), py::arg("ev_type"), py::arg("pod_entry"),
+        py::arg("ev_of"), py::arg("model_of"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("epoch"), py::arg("shard_id"),
+        py::arg("num_shards"), py::arg("max_tokens"), py::arg("algo") = 0);
 #else
   m.attr("HAS_HIP") = false;
 #endif

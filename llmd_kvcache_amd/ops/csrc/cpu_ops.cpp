@@ -10,6 +10,7 @@
 #include <torch/extension.h>
 
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "kvidx_common.h"
@@ -184,9 +185,26 @@ static int64_t emap_find(const TableView& v, uint64_t h, uint32_t model) {
 
 // ---- public ops ------------------------------------------------------
 
+// Chain function by native algo id (kvidx_common.h): 0 fnv-64a,
+// 1 sha256-cbor-64, 2 sha256-cbor-64-low.  The id is resolved once per
+// call, outside the chunk loops.
+template <typename F>
+static auto dispatch_algo(int64_t algo, F&& f) {
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  switch (algo) {
+    case ALGO_SHA256_HI:
+      return f(std::integral_constant<int, ALGO_SHA256_HI>{});
+    case ALGO_SHA256_LOW:
+      return f(std::integral_constant<int, ALGO_SHA256_LOW>{});
+    default:
+      return f(std::integral_constant<int, ALGO_FNV64A>{});
+  }
+}
+
 std::vector<uint64_t> tokens_to_chunk_hashes(std::vector<uint64_t> tokens,
                                              uint64_t parent,
-                                             int64_t block_size) {
+                                             int64_t block_size,
+                                             int64_t algo) {
   TORCH_CHECK(block_size > 0 && block_size <= 256,
               "block_size must be in (0, 256]");
   std::vector<uint32_t> toks(tokens.begin(), tokens.end());
@@ -194,27 +212,50 @@ std::vector<uint64_t> tokens_to_chunk_hashes(std::vector<uint64_t> tokens,
   std::vector<uint64_t> out;
   out.reserve(n_chunks);
   uint64_t h = parent;
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    h = chunk_hash(h, toks.data() + c * block_size, (int)block_size);
-    out.push_back(h);
-  }
+  dispatch_algo(algo, [&](auto A) {
+    for (int64_t c = 0; c < n_chunks; ++c) {
+      const uint32_t* t = toks.data() + c * block_size;
+      if constexpr (decltype(A)::value == ALGO_FNV64A)
+        h = chunk_hash(h, t, (int)block_size);
+      else
+        h = chunk_hash_sha256(h, t, (int)block_size,
+                              sha_digest_word(decltype(A)::value));
+      out.push_back(h);
+    }
+  });
   return out;
 }
 
-// Branchless-variant twin of tokens_to_chunk_hashes - exists so tests
-// can verify chunk_hash_fast (the GPU hot path) == chunk_hash on every
-// CBOR length-boundary case without a GPU.
+// Twin of tokens_to_chunk_hashes over the code the GPU hot path runs, so
+// tests can verify it on every CBOR / SHA padding boundary without a
+// GPU: chunk_hash_fast (branchless FNV) for algo 0, and the
+// encode-whole-payload-then-compress shape of k_hash_chain_tr
+// (chunk_hash_sha256_wave) for the SHA algos.
 std::vector<uint64_t> tokens_to_chunk_hashes_fast(
-    std::vector<uint64_t> tokens, uint64_t parent, int64_t block_size) {
+    std::vector<uint64_t> tokens, uint64_t parent, int64_t block_size,
+    int64_t algo) {
+  TORCH_CHECK(block_size > 0, "block_size must be positive");
   std::vector<uint32_t> toks(tokens.begin(), tokens.end());
   int64_t n_chunks = (int64_t)toks.size() / block_size;
   std::vector<uint64_t> out;
   out.reserve(n_chunks);
   uint64_t h = parent;
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    h = chunk_hash_fast(h, toks.data() + c * block_size, (int)block_size);
-    out.push_back(h);
-  }
+  std::vector<uint32_t> words(
+      16 * sha_blocks_for(sha_max_payload((int)block_size)));
+  dispatch_algo(algo, [&](auto A) {
+    for (int64_t c = 0; c < n_chunks; ++c) {
+      const uint32_t* t = toks.data() + c * block_size;
+      if constexpr (decltype(A)::value == ALGO_FNV64A) {
+        h = chunk_hash_fast(h, t, (int)block_size);
+      } else {
+        ShaHostBuf buf{words.data()};
+        h = chunk_hash_sha256_wave(h, t, (int)block_size,
+                                   sha_digest_word(decltype(A)::value), buf, true,
+                                   ShaHostAny{});
+      }
+      out.push_back(h);
+    }
+  });
   return out;
 }
 
@@ -223,9 +264,10 @@ std::vector<uint64_t> tokens_to_chunk_hashes_fast(
 // chunk-count offsets returned alongside.
 std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
                                          at::Tensor parents,
-                                         int64_t block_size) {
+                                         int64_t block_size, int64_t algo) {
   TORCH_CHECK(tokens.dtype() == at::kLong && offsets.dtype() == at::kLong &&
               parents.dtype() == at::kLong);
+  TORCH_CHECK(block_size > 0, "block_size must be positive");
   auto tok = tokens.contiguous();
   auto off = offsets.contiguous();
   auto par = parents.contiguous();
@@ -241,19 +283,25 @@ std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
   auto out = at::empty({cop[B]}, tokens.options());
   uint64_t* outp = reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>());
 
-  at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
-    std::vector<uint32_t> buf(block_size);
-    for (int64_t b = begin; b < end; ++b) {
-      uint64_t h = parp[b];
-      int64_t n_chunks = cop[b + 1] - cop[b];
-      const int64_t* t0 = tokp + offp[b];
-      for (int64_t c = 0; c < n_chunks; ++c) {
-        for (int64_t j = 0; j < block_size; ++j)
-          buf[j] = (uint32_t)t0[c * block_size + j];
-        h = chunk_hash(h, buf.data(), (int)block_size);
-        outp[cop[b] + c] = h;
+  dispatch_algo(algo, [&](auto A) {
+    at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
+      std::vector<uint32_t> buf(block_size);
+      for (int64_t b = begin; b < end; ++b) {
+        uint64_t h = parp[b];
+        int64_t n_chunks = cop[b + 1] - cop[b];
+        const int64_t* t0 = tokp + offp[b];
+        for (int64_t c = 0; c < n_chunks; ++c) {
+          for (int64_t j = 0; j < block_size; ++j)
+            buf[j] = (uint32_t)t0[c * block_size + j];
+          if constexpr (decltype(A)::value == ALGO_FNV64A)
+            h = chunk_hash(h, buf.data(), (int)block_size);
+          else
+            h = chunk_hash_sha256(h, buf.data(), (int)block_size,
+                                  sha_digest_word(decltype(A)::value));
+          outp[cop[b] + c] = h;
+        }
       }
-    }
+    });
   });
   return {out, chunk_off};
 }

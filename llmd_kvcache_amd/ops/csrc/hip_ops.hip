@@ -442,7 +442,9 @@ __global__ void __launch_bounds__(64) k_score_from_masks(
 
 // Batched hash chains: one LANE per prompt (chains are serial per prompt,
 // wave64-parallel across prompts; streaming CBOR->FNV keeps all state in
-// registers).
+// registers).  ALGO is the chain-function policy (kvidx_common.h
+// chain_link): 0 = fnv-64a, 1/2 = SHA-256 over the same payload.
+template <int ALGO>
 __global__ void k_hash_chain(const int64_t* __restrict__ tokens,
                              const int64_t* __restrict__ tok_off,  // [B+1]
                              const uint64_t* __restrict__ parents,
@@ -456,7 +458,7 @@ __global__ void k_hash_chain(const int64_t* __restrict__ tokens,
   int64_t n_chunks = chunk_off[b + 1] - chunk_off[b];
   uint64_t* o = out + chunk_off[b];
   for (int64_t c = 0; c < n_chunks; ++c) {
-    h = chunk_hash_fast(h, t0 + c * block_size, block_size);
+    h = chain_link<ALGO>(h, t0 + c * block_size, block_size);
     o[c] = h;
   }
 }
@@ -476,13 +478,67 @@ __global__ void k_hash_chain(const int64_t* __restrict__ tokens,
 // dependent-ALU-latency-bound at 1 wave/SIMD, and ILP-x recovers ~x of
 // that latency.  Lane l of the grid owns prompts {l, l+L, .., l+(ILP-1)L}
 // where L = total lanes, keeping every token load coalesced.
-template <int BS, int ILP>
+//
+// SHA-256 policy (ALGO 1/2, ILP 1): not a re-skin of the FNV body.  FNV
+// streams bytes through one 64-bit register; SHA-256 needs 16-word
+// blocks and CBOR makes every byte position data-dependent per lane.
+// Each lane therefore first packs its whole padded payload (1..6 blocks
+// depending on BS and the token widths) into its own LDS column - layout
+// [word][thread], so lanes at the same word index hit distinct banks and
+// the data-dependent word index costs an LDS address, not scratch - and
+// then the wave runs the fully unrolled 64-round compression together
+// for the wave-maximum block count, a per-lane select discarding blocks
+// a lane does not have (chunk_hash_sha256_wave).  The workgroup is
+// SHA_TR_THREADS(BS) wide so the columns stay <= 48 KB per workgroup.
+template <int NT>
+struct ShaLdsCol {
+  uint32_t* p;  // &words[0][threadIdx.x]
+  DEV void st(int i, uint32_t v) { p[i * NT] = v; }
+  DEV uint32_t ld(int i) const { return p[i * NT]; }
+};
+struct ShaWaveAny {
+  DEV bool operator()(bool b) const { return __any(b); }
+};
+constexpr int sha_tr_threads(int bs) { return bs > 32 ? 128 : 256; }
+constexpr int sha_tr_words(int bs) {
+  return 16 * sha_blocks_for(sha_max_payload(bs));
+}
+
+template <int BS, int ILP, int ALGO = ALGO_FNV64A>
 __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
                                 const uint64_t* __restrict__ parents,  // [B]
                                 const int32_t* __restrict__ n_chunks,  // [B]
                                 int64_t B, int64_t L, int max_chunks,
                                 int row_major,
                                 uint64_t* __restrict__ out) {  // [maxC,B] or [B,maxC]
+  if constexpr (ALGO != ALGO_FNV64A) {
+    static_assert(ILP == 1, "the SHA chain runs one prompt per lane");
+    constexpr int NT = sha_tr_threads(BS);
+    __shared__ uint32_t sha_words[sha_tr_words(BS) * NT];
+    const int64_t lane = (int64_t)blockIdx.x * NT + threadIdx.x;
+    // no early return: idle lanes ride along (clamped loads, results
+    // discarded) so every wave-wide vote below sees whole waves
+    const bool live = lane < B;
+    const int64_t bi = live ? lane : 0;
+    uint64_t h = parents[bi];
+    const int mc = live ? n_chunks[bi] : 0;
+    ShaLdsCol<NT> col{sha_words + threadIdx.x};
+    for (int c = 0; c < max_chunks; ++c) {
+      const bool active = c < mc;
+      if (!__any(active)) break;  // wave-uniform: chains only get shorter
+      uint32_t tok[BS];
+#pragma unroll
+      for (int j = 0; j < BS; ++j)
+        tok[j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * B + bi];
+      const uint64_t h2 = chunk_hash_sha256_wave(
+          h, tok, BS, sha_digest_word(ALGO), col, active, ShaWaveAny{});
+      h = active ? h2 : h;
+      if (active)
+        out[row_major ? (int64_t)lane * max_chunks + c
+                      : (int64_t)c * B + lane] = h;
+    }
+    return;
+  }
   const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= L) return;
   int64_t b[ILP];
@@ -567,6 +623,7 @@ __global__ void k_hash_chain_tr_pf(const int32_t* __restrict__ tokens_t,
 // request-key chain (token_processor.go:94-123, stitched from the parent
 // engine key via the engine map like pool.go:279-296) and all 64 lanes
 // fan out the per-block inserts.
+template <int ALGO>
 __global__ void k_apply_events(
     DevTable v, const int64_t* __restrict__ tokens,
     const int32_t* __restrict__ tok_off,     // [E+1]
@@ -628,7 +685,7 @@ __global__ void k_apply_events(
       const int64_t* t0 = tokens + tok_off[e];
       uint64_t h = parent;
       for (int c = 0; c < n_chunks; ++c) {
-        h = chunk_hash_fast(h, t0 + (int64_t)c * block_size, block_size);
+        h = chain_link<ALGO>(h, t0 + (int64_t)c * block_size, block_size);
         req[c] = h;
       }
     }
@@ -697,6 +754,7 @@ DEV int64_t dev_bmap_find(const uint64_t* __restrict__ bkeys,
 // request-key chains into req_scratch.  Parent resolution: earlier block
 // of the SAME group in this batch (bmap) first, then the persistent
 // engine map (cross-batch), else the chain root.
+template <int ALGO>
 __global__ void k_event_chains(
     DevTable v, const int64_t* __restrict__ tokens,
     const int32_t* __restrict__ tok_off, const uint64_t* __restrict__ ehashes,
@@ -734,7 +792,7 @@ __global__ void k_event_chains(
     uint64_t h = parent;
     const int n_ins = min(n_chunks, nh);
     for (int c = 0; c < n_ins; ++c) {
-      h = chunk_hash_fast(h, t0 + (int64_t)c * block_size, block_size);
+      h = chain_link<ALGO>(h, t0 + (int64_t)c * block_size, block_size);
       req_scratch[eh_off[e] + c] = h;
     }
   }
@@ -764,6 +822,7 @@ __global__ void k_transpose_ev_tokens(const int32_t* __restrict__ flat,
     out[(int64_t)i * E + e] = flat[tok_off[e] + i];
 }
 
+template <int ALGO>
 __global__ void k_event_chains_ev(
     DevTable v, const int32_t* __restrict__ tokens_t,  // [maxT, E]
     const int32_t* __restrict__ tok_off, const uint64_t* __restrict__ ehashes,
@@ -788,7 +847,7 @@ __global__ void k_event_chains_ev(
   for (int c = 0; c < n_chunks; ++c) {
     for (int j = 0; j < block_size; ++j)
       tok[j] = (uint32_t)tokens_t[(int64_t)(c * block_size + j) * E + e];
-    h = chunk_hash_fast(h, tok, block_size);
+    h = chain_link<ALGO>(h, tok, block_size);
     req_scratch[eh_off[e] + c] = h;
   }
 }
@@ -1020,10 +1079,30 @@ at::Tensor gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
   return scores;
 }
 
+// Runs f(std::integral_constant<int, ALGO>) for a native chain algo id
+// (0 fnv-64a, 1 sha256-cbor-64, 2 sha256-cbor-64-low): the id picks a
+// kernel instantiation on the host, never a branch inside a kernel.
+template <typename F>
+static void dispatch_algo(int64_t algo, F&& f) {
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  switch (algo) {
+    case ALGO_SHA256_HI:
+      f(std::integral_constant<int, ALGO_SHA256_HI>{});
+      break;
+    case ALGO_SHA256_LOW:
+      f(std::integral_constant<int, ALGO_SHA256_LOW>{});
+      break;
+    default:
+      f(std::integral_constant<int, ALGO_FNV64A>{});
+      break;
+  }
+}
+
 std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
                                        at::Tensor parents,
-                                       int64_t block_size) {
+                                       int64_t block_size, int64_t algo) {
   TORCH_CHECK(tokens.is_cuda());
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
   int64_t B = parents.numel();
   auto chunk_off_cpu = at::zeros({B + 1}, at::kLong);
   {
@@ -1039,11 +1118,13 @@ std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
   if (B == 0) return {out, chunk_off};
   int threads = 256;
   int blocks = (int)((B + threads - 1) / threads);
-  hipLaunchKernelGGL(k_hash_chain, dim3(blocks), dim3(threads), 0, STREAM,
-                     tokens.data_ptr<int64_t>(), tok_off.data_ptr<int64_t>(),
-                     U64P(parents), chunk_off.data_ptr<int64_t>(), B,
-                     (int)block_size,
-                     reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
+  dispatch_algo(algo, [&](auto A) {
+    hipLaunchKernelGGL(k_hash_chain<decltype(A)::value>, dim3(blocks),
+                       dim3(threads), 0, STREAM, tokens.data_ptr<int64_t>(),
+                       tok_off.data_ptr<int64_t>(), U64P(parents),
+                       chunk_off.data_ptr<int64_t>(), B, (int)block_size,
+                       reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
+  });
   return {out, chunk_off};
 }
 
@@ -1052,8 +1133,9 @@ std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
 at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
                              at::Tensor n_chunks, int64_t block_size,
                              int64_t max_chunks, int64_t ilp,
-                             int64_t row_major) {
+                             int64_t row_major, int64_t algo) {
   TORCH_CHECK(tokens_t.is_cuda() && tokens_t.dtype() == at::kInt);
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
   TORCH_CHECK(tokens_t.dim() == 2, "tokens_t must be [T, B]");
   int64_t B = tokens_t.size(1);
   TORCH_CHECK(parents.numel() == B && n_chunks.numel() == B);
@@ -1063,6 +1145,38 @@ at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
                                  : std::initializer_list<int64_t>{max_chunks, B},
                        parents.options());
   if (B == 0 || max_chunks == 0) return out;
+  if (algo != ALGO_FNV64A) {
+    // SHA-256 chains: one prompt per lane (ilp is an FNV tuning knob and
+    // is ignored), workgroup width set by the LDS payload columns.
+    TORCH_CHECK(tokens_t.size(0) >= max_chunks * block_size,
+                "tokens_t has fewer rows than max_chunks * block_size");
+    auto tokens_c = tokens_t.contiguous();
+    auto launch_sha = [&](auto kern, int threads) {
+      int blocks = (int)((B + threads - 1) / threads);
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, STREAM,
+                         tokens_c.data_ptr<int32_t>(), U64P(parents),
+                         n_chunks.data_ptr<int32_t>(), B, B, (int)max_chunks,
+                         (int)row_major,
+                         reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
+    };
+    dispatch_algo(algo, [&](auto A) {
+      constexpr int AL = decltype(A)::value;
+      if constexpr (AL != ALGO_FNV64A) {
+        switch (block_size) {
+          case 4:  launch_sha(k_hash_chain_tr<4, 1, AL>, sha_tr_threads(4)); break;
+          case 8:  launch_sha(k_hash_chain_tr<8, 1, AL>, sha_tr_threads(8)); break;
+          case 16: launch_sha(k_hash_chain_tr<16, 1, AL>, sha_tr_threads(16)); break;
+          case 32: launch_sha(k_hash_chain_tr<32, 1, AL>, sha_tr_threads(32)); break;
+          case 64: launch_sha(k_hash_chain_tr<64, 1, AL>, sha_tr_threads(64)); break;
+          default:
+            TORCH_CHECK(false, "hash_chain_tr supports block sizes "
+                               "4/8/16/32/64; use gpu_hash_chain for other "
+                               "sizes");
+        }
+      }
+    });
+    return out;
+  }
   // ILP trades wave count for per-lane chain interleave: only pay the
   // wave reduction when there are waves to spare (tuned by
   // scripts/sweep_chain.py on MI355X).
@@ -1128,7 +1242,8 @@ void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
                       at::Tensor ev_type, at::Tensor pod_entry,
                       at::Tensor grp_off, at::Tensor model_of,
                       int64_t init_hash_bits, int64_t block_size,
-                      int64_t epoch, int64_t shard_id, int64_t num_shards) {
+                      int64_t epoch, int64_t shard_id, int64_t num_shards,
+                      int64_t algo) {
   auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
                     pods_per_key);
   int64_t G = grp_off.numel() - 1;
@@ -1139,8 +1254,10 @@ void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
                                ehashes.options());
   const int waves_per_block = 4;
   int blocks = (int)((G + waves_per_block - 1) / waves_per_block);
+  dispatch_algo(algo, [&](auto A) {
   hipLaunchKernelGGL(
-      k_apply_events, dim3(blocks), dim3(waves_per_block * 64), 0, STREAM, v,
+      k_apply_events<decltype(A)::value>, dim3(blocks),
+      dim3(waves_per_block * 64), 0, STREAM, v,
       tokens.data_ptr<int64_t>(), tok_off.data_ptr<int32_t>(), U64P(ehashes),
       eh_off.data_ptr<int32_t>(), U64P(parents),
       has_parent.data_ptr<uint8_t>(), ev_type.data_ptr<uint8_t>(),
@@ -1149,6 +1266,7 @@ void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
       (uint64_t)init_hash_bits, (int)block_size, (int32_t)epoch,
       (int)shard_id, (int)num_shards,
       reinterpret_cast<uint64_t*>(req_scratch.data_ptr<int64_t>()));
+  });
 }
 
 // Transposed-chain phase-split apply: NO batch-local parents (host
@@ -1163,7 +1281,7 @@ void gpu_apply_events_split_tr(
     at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
     at::Tensor ev_of, at::Tensor model_of, int64_t init_hash_bits,
     int64_t block_size, int64_t epoch, int64_t shard_id,
-    int64_t num_shards, int64_t max_tokens) {
+    int64_t num_shards, int64_t max_tokens, int64_t algo) {
   auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
                     pods_per_key);
   TORCH_CHECK(tokens_flat.dtype() == at::kInt,
@@ -1187,7 +1305,8 @@ void gpu_apply_events_split_tr(
                        tokens_t.data_ptr<int32_t>());
   }
   TORCH_CHECK(model_of.numel() == E, "model_of must have one id per event");
-  hipLaunchKernelGGL(k_event_chains_ev,
+  dispatch_algo(algo, [&](auto A) {
+  hipLaunchKernelGGL(k_event_chains_ev<decltype(A)::value>,
                      dim3((int)((E + threads - 1) / threads)), dim3(threads),
                      0, STREAM, v, tokens_t.data_ptr<int32_t>(),
                      tok_off.data_ptr<int32_t>(), U64P(ehashes),
@@ -1198,6 +1317,7 @@ void gpu_apply_events_split_tr(
                      (uint64_t)init_hash_bits, (int)block_size,
                      reinterpret_cast<uint64_t*>(
                          req_scratch.data_ptr<int64_t>()));
+  });
   hipLaunchKernelGGL(k_event_inserts,
                      dim3((int)((n + threads - 1) / threads)), dim3(threads),
                      0, STREAM, v, U64P(ehashes), eh_off.data_ptr<int32_t>(),
@@ -1222,7 +1342,7 @@ void gpu_apply_events_split(
     at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
     at::Tensor grp_off, at::Tensor ev_of, at::Tensor model_of,
     int64_t init_hash_bits, int64_t block_size, int64_t epoch,
-    int64_t shard_id, int64_t num_shards) {
+    int64_t shard_id, int64_t num_shards, int64_t algo) {
   auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
                     pods_per_key);
   int64_t G = grp_off.numel() - 1;
@@ -1242,7 +1362,8 @@ void gpu_apply_events_split(
                      bvals.data_ptr<int32_t>(), bcap - 1);
   TORCH_CHECK(model_of.numel() == ev_type.numel(),
               "model_of must have one id per event");
-  hipLaunchKernelGGL(k_event_chains,
+  dispatch_algo(algo, [&](auto A) {
+  hipLaunchKernelGGL(k_event_chains<decltype(A)::value>,
                      dim3((int)((G + threads - 1) / threads)), dim3(threads),
                      0, STREAM, v, tokens.data_ptr<int64_t>(),
                      tok_off.data_ptr<int32_t>(), U64P(ehashes),
@@ -1256,6 +1377,7 @@ void gpu_apply_events_split(
                      bvals.data_ptr<int32_t>(), bcap - 1,
                      reinterpret_cast<uint64_t*>(
                          req_scratch.data_ptr<int64_t>()));
+  });
   hipLaunchKernelGGL(k_event_inserts,
                      dim3((int)((n + threads - 1) / threads)), dim3(threads),
                      0, STREAM, v, U64P(ehashes), eh_off.data_ptr<int32_t>(),

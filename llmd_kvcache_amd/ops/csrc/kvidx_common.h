@@ -198,6 +198,307 @@ KVIDX_HD uint64_t chunk_hash(uint64_t parent, const TokT* tokens, int n) {
   return h;
 }
 
+// ---------------------------------------------------------------------
+// SHA-256 chain link (hash_algo "sha256-cbor-64" / "sha256-cbor-64-low"):
+// SHA-256 over the same canonical-CBOR payload, 64 digest bits kept.
+// Native algo ids (utils/hashing.py NATIVE_ALGO_IDS is the one place
+// that maps names to them):
+//   0 fnv-64a            (everything above)
+//   1 sha256-cbor-64     digest bytes 0..8  big-endian = state H0:H1
+//   2 sha256-cbor-64-low digest bytes 24..32 big-endian = state H6:H7
+//
+// Two drivers share the byte packer, the CBOR item builders and the
+// compression function:
+//  - chunk_hash_sha256: streaming through one 16-word block buffer,
+//    compressing whenever it fills (host ops and the GPU kernels whose
+//    chains are not wave-dense);
+//  - chunk_hash_sha256_wave: encodes the WHOLE padded payload into a
+//    caller-provided word buffer first (an LDS column on the GPU), then
+//    runs the compression for the wave-maximum block count with a
+//    per-lane select - every lane compresses at the same time, so the 64
+//    rounds never diverge (the read-path kernel k_hash_chain_tr).
+// ---------------------------------------------------------------------
+
+static constexpr int ALGO_FNV64A = 0;
+static constexpr int ALGO_SHA256_HI = 1;
+static constexpr int ALGO_SHA256_LOW = 2;
+
+KVIDX_HD bool algo_valid(int64_t algo) { return algo >= 0 && algo <= 2; }
+// First state word of the 64 bits an algo keeps.
+KVIDX_HD constexpr int sha_digest_word(int algo) {
+  return algo == ALGO_SHA256_LOW ? 6 : 0;
+}
+
+// Largest payload [parent, n tokens, null] in bytes, and the SHA block
+// count it pads to (0x80 + 8 length bytes appended).
+KVIDX_HD constexpr int sha_max_payload(int n) {
+  return 1 + 9 + (n < 24 ? 1 : n <= 0xFF ? 2 : n <= 0xFFFF ? 3 : 5) + 5 * n +
+         1;
+}
+KVIDX_HD constexpr int sha_blocks_for(int payload_bytes) {
+  return (payload_bytes + 9 + 63) >> 6;
+}
+
+KVIDX_HD uint32_t sha_rotr(uint32_t x, int n) {
+  return (x >> n) | (x << (32 - n));
+}
+
+// One SHA-256 block.  Rounds are fully unrolled on the device so the
+// rolling 16-word schedule is indexed statically (a dynamically indexed
+// w[] would live in scratch).
+KVIDX_HD void sha256_compress(uint32_t st[8], uint32_t w[16]) {
+  constexpr uint32_t K[64] = {
+      0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu,
+      0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u,
+      0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u,
+      0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu,
+      0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau, 0x983e5152u,
+      0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u,
+      0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu,
+      0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+      0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u,
+      0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u,
+      0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu,
+      0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
+      0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+  uint32_t a = st[0], b = st[1], c = st[2], d = st[3];
+  uint32_t e = st[4], f = st[5], g = st[6], h = st[7];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 64; ++i) {
+    if (i >= 16) {
+      const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
+      w[i & 15] += (sha_rotr(w15, 7) ^ sha_rotr(w15, 18) ^ (w15 >> 3)) +
+                   w[(i - 7) & 15] +
+                   (sha_rotr(w2, 17) ^ sha_rotr(w2, 19) ^ (w2 >> 10));
+    }
+    const uint32_t t1 = h +
+                        (sha_rotr(e, 6) ^ sha_rotr(e, 11) ^ sha_rotr(e, 25)) +
+                        ((e & f) ^ (~e & g)) + K[i] + w[i & 15];
+    const uint32_t t2 = (sha_rotr(a, 2) ^ sha_rotr(a, 13) ^ sha_rotr(a, 22)) +
+                        ((a & b) ^ (a & c) ^ (b & c));
+    h = g; g = f; f = e; e = d + t1;
+    d = c; c = b; b = a; a = t1 + t2;
+  }
+  st[0] += a; st[1] += b; st[2] += c; st[3] += d;
+  st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+
+KVIDX_HD void sha256_iv(uint32_t st[8]) {
+  st[0] = 0x6a09e667u; st[1] = 0xbb67ae85u; st[2] = 0x3c6ef372u;
+  st[3] = 0xa54ff53au; st[4] = 0x510e527fu; st[5] = 0x9b05688cu;
+  st[6] = 0x1f83d9abu; st[7] = 0x5be0cd19u;
+}
+
+// Canonical-CBOR unsigned (<= 32 bit) as a LEFT-aligned big-endian byte
+// string in a u64 (header first); *len gets its 1..5 bytes.  Branchless.
+KVIDX_HD uint64_t sha_cbor_u32_item(uint32_t v, uint8_t major, int* len) {
+  const uint8_t mt = major << 5;
+  const int sel = (v >= 24) + (v > 0xFF) + (v > 0xFFFF);  // 0..3
+  const int n = sel == 3 ? 4 : sel;                       // value bytes
+  const uint8_t header = sel ? (uint8_t)(mt | (0x17 + sel))
+                             : (uint8_t)(mt | v);
+  *len = 1 + n;
+  // n == 0: the value lives in the header byte; v << 56 must not be OR-ed
+  const uint64_t val = sel ? ((uint64_t)v << (56 - 8 * n)) : 0ull;
+  return ((uint64_t)header << 56) | val;
+}
+
+// Item k of the padded-payload byte stream of one chain link, as a
+// left-aligned byte string (<= 5 bytes) in a u64:
+//   0: 0x83 + parent header   1/2: parent value, high / low <= 4 bytes
+//   3: array(n) header        4..3+n: tokens   4+n: null (0xF6)
+//   5+n: the SHA pad byte 0x80 (not part of the payload length)
+// Branchless per item; with a compile-time k the selection folds away.
+KVIDX_HD constexpr int sha_chunk_items(int n) { return n + 6; }
+
+template <typename TokT>
+KVIDX_HD uint64_t sha_chunk_item(int k, uint64_t parent, const TokT* tokens,
+                                 int n, int* len) {
+  if (k < 3) {
+    const int sel = (parent >= 24) + (parent > 0xFF) + (parent > 0xFFFF) +
+                    (parent > 0xFFFFFFFFull);            // 0..4
+    const int nv = sel == 0 ? 0 : (1 << (sel - 1));      // 0,1,2,4,8
+    if (k == 0) {
+      const uint8_t ph = sel ? (uint8_t)(0x17 + sel) : (uint8_t)parent;
+      *len = 2;
+      return (0x83ull << 56) | ((uint64_t)ph << 48);
+    }
+    if (k == 1) {
+      const int n_hi = nv == 8 ? 4 : 0;
+      *len = n_hi;
+      return n_hi ? (parent >> 32) << 32 : 0ull;
+    }
+    const int n_lo = nv == 8 ? 4 : nv;
+    *len = n_lo;
+    return n_lo ? (uint64_t)(uint32_t)parent << (64 - 8 * n_lo) : 0ull;
+  }
+  if (k == 3) return sha_cbor_u32_item((uint32_t)n, 4, len);
+  if (k < 4 + n) return sha_cbor_u32_item((uint32_t)tokens[k - 4], 0, len);
+  *len = 1;
+  return (k == 4 + n ? 0xF6ull : 0x80ull) << 56;
+}
+
+// Big-endian byte packer.  acc holds the `fill` (< 4) pending bytes
+// left-aligned; bits past them are zero.  put() leaves the next two
+// words in hi/lo (lo possibly partial, zero-padded) and says how many of
+// them (adv, 0..2) are complete.  Callers store BOTH words at their
+// write index and advance by adv: a partial word is simply overwritten
+// by its completed version, so there is no data-dependent store.
+struct ShaPacker {
+  uint64_t acc = 0;
+  int fill = 0;
+  int nbytes = 0;
+  uint32_t hi = 0, lo = 0;
+  // item: left-aligned bytes, len <= 5 (fill + len <= 8 fits acc)
+  KVIDX_HD int put(uint64_t item, int len) {
+    acc |= item >> (8 * fill);
+    fill += len;
+    nbytes += len;
+    const int adv = fill >> 2;
+    hi = (uint32_t)(acc >> 32);
+    lo = (uint32_t)acc;
+    acc = adv == 0 ? acc : adv == 1 ? (acc << 32) : 0ull;
+    fill &= 3;
+    return adv;
+  }
+};
+
+// One chain link, streamed through a single block buffer:
+// SHA-256(CBOR([parent, tokens[0..n), null])), returning state words
+// digest_word:digest_word+1 as a big-endian u64.  The loop has ONE
+// compression site; w[16..17] catch the word pair that straddles a block
+// boundary and are carried down after the block is consumed.
+template <typename TokT>
+KVIDX_HD uint64_t chunk_hash_sha256(uint64_t parent, const TokT* tokens, int n,
+                                    int digest_word) {
+  uint32_t st[8];
+  uint32_t w[18];
+  w[16] = w[17] = 0;  // carried down before they are first written
+  sha256_iv(st);
+  ShaPacker p;
+  const int n_items = sha_chunk_items(n);
+  int widx = 0, k = 0;
+  bool tail_done = false, finished = false;
+  for (;;) {
+    if (widx >= 16) {
+      sha256_compress(st, w);
+      w[0] = w[16];
+      w[1] = w[17];
+      widx -= 16;
+      if (finished) break;
+    }
+    if (k < n_items) {
+      int len;
+      const uint64_t item = sha_chunk_item(k++, parent, tokens, n, &len);
+      const int adv = p.put(item, len);
+      w[widx] = p.hi;
+      w[widx + 1] = p.lo;
+      widx += adv;
+    } else if (!tail_done) {
+      widx += p.fill ? 1 : 0;  // the partial word is already in w[widx]
+      tail_done = true;
+    } else if (widx == 14) {   // 64-bit big-endian bit length
+      w[14] = 0;
+      w[15] = (uint32_t)(p.nbytes - 1) * 8u;  // minus the 0x80 pad byte
+      widx = 16;
+      finished = true;
+    } else {
+      w[widx++] = 0;
+    }
+  }
+  uint64_t out = 0;
+  for (int i = 0; i < 8; i += 2)  // static indices only (no st[] in scratch)
+    if (i == digest_word) out = ((uint64_t)st[i] << 32) | st[i + 1];
+  return out;
+}
+
+// Wave-convergent chain link.  buf (st(i, v) / ld(i)) must hold
+// 16 * sha_blocks_for(sha_max_payload(n)) words private to this lane - an
+// LDS column on the GPU.  Each lane first encodes its WHOLE padded
+// payload, then the compression runs for the wave-maximum block count
+// with a per-lane select dropping the blocks a lane does not have, so
+// the 64 rounds never diverge.  any(p) is the wave-wide OR of p
+// (identity on the host).  `active`: this lane's result is wanted (idle
+// lanes compute and the caller discards).
+template <typename TokT, class Buf, class AnyFn>
+KVIDX_HD uint64_t chunk_hash_sha256_wave(uint64_t parent, const TokT* tokens,
+                                         int n, int digest_word, Buf& buf,
+                                         bool active, AnyFn any) {
+  const int max_blocks = sha_blocks_for(sha_max_payload(n));
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < max_blocks * 16; ++i) buf.st(i, 0u);
+  ShaPacker p;
+  int widx = 0;
+  const int n_items = sha_chunk_items(n);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int k = 0; k < n_items; ++k) {
+    int len;
+    const uint64_t item = sha_chunk_item(k, parent, tokens, n, &len);
+    const int adv = p.put(item, len);
+    buf.st(widx, p.hi);
+    buf.st(widx + 1, p.lo);
+    widx += adv;
+  }
+  const int payload = p.nbytes - 1;  // minus the 0x80 pad byte
+  const int nblk = sha_blocks_for(payload);
+  buf.st(nblk * 16 - 1, (uint32_t)payload * 8u);
+  uint32_t st[8];
+  sha256_iv(st);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int blk = 0; blk < max_blocks; ++blk) {
+    const bool mine = blk < nblk;
+    if (!any(active && mine)) break;
+    uint32_t w[16], nx[8];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 16; ++i) w[i] = buf.ld(blk * 16 + i);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 8; ++i) nx[i] = st[i];
+    sha256_compress(nx, w);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 8; ++i) st[i] = mine ? nx[i] : st[i];
+  }
+  uint64_t out = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 8; i += 2)
+    if (i == digest_word) out = ((uint64_t)st[i] << 32) | st[i + 1];
+  return out;
+}
+
+// Plain word buffer for the host build of chunk_hash_sha256_wave.
+struct ShaHostBuf {
+  uint32_t* p;
+  KVIDX_HD void st(int i, uint32_t v) { p[i] = v; }
+  KVIDX_HD uint32_t ld(int i) const { return p[i]; }
+};
+struct ShaHostAny {
+  KVIDX_HD bool operator()(bool b) const { return b; }
+};
+
+// Compile-time chain policy used by the kernels and host ops.
+template <int ALGO, typename TokT>
+KVIDX_HD uint64_t chain_link(uint64_t parent, const TokT* tokens, int n) {
+  if constexpr (ALGO == ALGO_FNV64A)
+    return chunk_hash_fast(parent, tokens, n);
+  else
+    return chunk_hash_sha256(parent, tokens, n, sha_digest_word(ALGO));
+}
+
 KVIDX_HD uint32_t make_pod_entry(uint32_t pod_id, uint32_t tier) {
   return ((tier & 0xFu) << 24) | ((pod_id + 1) & 0x00FFFFFFu);
 }

@@ -58,7 +58,7 @@ namespace kvidx {
 
 // cpu_ops.cpp / hip_ops.hip (same extension)
 std::vector<at::Tensor> hash_chain_batch(at::Tensor, at::Tensor, at::Tensor,
-                                         int64_t);
+                                         int64_t, int64_t);
 at::Tensor cpu_fused_score(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                            at::Tensor, at::Tensor, at::Tensor, int64_t,
                            at::Tensor, at::Tensor, int64_t, at::Tensor,
@@ -1084,10 +1084,11 @@ at::Tensor wire_score_flat(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
                            at::Tensor filter_words, at::Tensor weights,
                            int64_t num_pods, int64_t epoch,
                            int64_t init_hash_bits, int64_t block_size,
-                           int64_t n_tiers) {
+                           int64_t n_tiers, int64_t algo) {
   int64_t B = offsets.numel() - 1;
   auto parents = at::full({B}, init_hash_bits, at::kLong);
-  auto chained = hash_chain_batch(tokens_flat, offsets, parents, block_size);
+  auto chained =
+      hash_chain_batch(tokens_flat, offsets, parents, block_size, algo);
   at::Tensor hashes = chained[0];
   at::Tensor chunk_off = chained[1];  // int64 [B+1]
   bool is_cuda = keys.is_cuda();
@@ -1131,7 +1132,13 @@ at::Tensor wire_score_flat(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
 }
 
 void register_wirefront(py::module_& m) {
-  m.def("wire_score_flat", &wire_score_flat,
+  m.def("wire_score_flat", &wire_score_flat, py::arg("keys"),
+        py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("offsets"),
+        py::arg("model_id"), py::arg("filter_words"), py::arg("weights"),
+        py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("n_tiers"), py::arg("algo") = 0,
         py::call_guard<py::gil_scoped_release>());
   py::class_<WireFront, std::shared_ptr<WireFront>>(m, "WireFront")
       .def(py::init<py::object, py::object, int64_t, int64_t>(),

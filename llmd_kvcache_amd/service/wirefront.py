@@ -27,6 +27,7 @@ from __future__ import annotations
 from typing import List, Sequence, Tuple
 
 from ..indexer import Indexer
+from ..utils import hashing
 
 
 class WireIndexerService:
@@ -38,10 +39,13 @@ class WireIndexerService:
         if not hasattr(ops, "WireFront"):
             raise RuntimeError(
                 "native extension built without the wirefront - rebuild")
-        if indexer.tokens_processor.config.hash_algo != "fnv-64a":
+        algo = indexer.tokens_processor.config.hash_algo
+        if algo not in hashing.NATIVE_ALGO_IDS:
             raise ValueError(
-                "wirefront requires the fnv-64a chain (the native "
-                "scoring op implements that algorithm)")
+                f"wirefront requires a chain hash with a native "
+                f"implementation ({sorted(hashing.NATIVE_ALGO_IDS)}); "
+                f"got {algo!r}")
+        self._algo_id = hashing.NATIVE_ALGO_IDS[algo]
         self.indexer = indexer
         self._front = ops.WireFront(self._score_tokens_cb,
                                     self._score_text_cb, max_batch,
@@ -112,7 +116,8 @@ class WireIndexerService:
          bs) = self._stage(model, pods)
         scores = self._run_flat(
             idx, *idx.table._t(), tokens_flat, offsets, model_id, filt,
-            weights, num_pods, idx.table.next_epoch(), init, bs, n_tiers)
+            weights, num_pods, idx.table.next_epoch(), init, bs, n_tiers,
+            self._algo_id)
         return scores, list(idx.registry.id_to_pod)
 
     def _score_text_cb(self, model: str, pods: Sequence[str],
@@ -139,7 +144,8 @@ class WireIndexerService:
          bs) = self._stage(model, pods)
         scores = self._run_flat(
             idx, *idx.table._t(), flat_t, off_t, model_id, filt, weights,
-            num_pods, idx.table.next_epoch(), init, bs, n_tiers)
+            num_pods, idx.table.next_epoch(), init, bs, n_tiers,
+            self._algo_id)
         # 4-tuple: the C++ side feeds elements 2/3 (int32 tokens +
         # offsets) into its prompt cache so repeats skip Python
         return (scores, list(idx.registry.id_to_pod),

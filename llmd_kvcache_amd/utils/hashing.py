@@ -82,16 +82,19 @@ def init_hash(seed: str = "") -> int:
 # -- pluggable hash algorithms (vLLM changed SHA-256 ->
 # FNV-64a once already; keep the chain function swappable) --------------
 
+def _sha256_digest(parent_hash: int, tokens) -> bytes:
+    import hashlib
+
+    return hashlib.sha256(cbor_chunk_payload(parent_hash, tokens)).digest()
+
+
 def sha256_cbor_64(parent_hash: int, tokens) -> int:
     """Alternative chain link: top 8 bytes (big-endian) of SHA-256 over
     the same canonical-CBOR payload - the shape of vLLM's historical
-    sha256 content addressing. NOTE: gated to host paths until a vLLM
-    golden fixture pins the exact byte convention (ROADMAP #5); the
-    HIP/C++ fast paths implement fnv-64a only."""
-    import hashlib
-
-    digest = hashlib.sha256(cbor_chunk_payload(parent_hash, tokens)).digest()
-    return int.from_bytes(digest[:8], "big")
+    sha256 content addressing.  Pinned to ``hashlib`` only; this Python
+    function is the golden for the native paths (C++ ops and the gfx950
+    kernels, native algo id 1)."""
+    return int.from_bytes(_sha256_digest(parent_hash, tokens)[:8], "big")
 
 
 def sha256_init_hash(seed: str = "") -> int:
@@ -101,7 +104,37 @@ def sha256_init_hash(seed: str = "") -> int:
         hashlib.sha256(seed.encode("utf-8")).digest()[:8], "big")
 
 
+def sha256_cbor_64_low(parent_hash: int, tokens) -> int:
+    """Chain link keeping digest bytes 24..32 (big-endian): the LOW 64
+    bits of the SHA-256 digest read as one big integer (native algo id
+    2).  This is believed to be the convention of vLLM's 64-bit
+    sha256-cbor option, but it is pinned here only to ``hashlib`` - no
+    vLLM golden fixture backs it yet, and that fixture (ROADMAP #2)
+    remains the arbiter of the byte convention."""
+    return int.from_bytes(_sha256_digest(parent_hash, tokens)[24:32], "big")
+
+
+def sha256_low_init_hash(seed: str = "") -> int:
+    """Chain root for ``sha256-cbor-64-low``: the same byte selection
+    over sha256(seed)."""
+    import hashlib
+
+    return int.from_bytes(
+        hashlib.sha256(seed.encode("utf-8")).digest()[24:32], "big")
+
+
 CHAIN_ALGOS = {
     "fnv-64a": (chunk_hash, init_hash),
     "sha256-cbor-64": (sha256_cbor_64, sha256_init_hash),
+    "sha256-cbor-64-low": (sha256_cbor_64_low, sha256_low_init_hash),
+}
+
+# Algo name -> id understood by the native layer (ops/csrc: the trailing
+# ``algo`` argument of the chain ops and kernels).  The only place that
+# knows the numbers; an algo missing here has no C++/HIP path and runs
+# in Python.
+NATIVE_ALGO_IDS = {
+    "fnv-64a": 0,
+    "sha256-cbor-64": 1,
+    "sha256-cbor-64-low": 2,
 }

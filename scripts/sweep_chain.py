@@ -1,7 +1,19 @@
 """Hash-chain kernel sweep on MI355X: batch x ILP grid.
 
     python scripts/sweep_chain.py
+    python scripts/sweep_chain.py --algo fnv-64a,sha256-cbor-64 \
+        --batches 512,4096,32768 --ilp 1 --repeats 5
+
+--algo takes one or more hash_algo names (utils.hashing.NATIVE_ALGO_IDS);
+with several, each batch size is measured for every algo back to back in
+the same process, so the rows are directly comparable.  ILP is an FNV
+tuning knob: the SHA-256 kernel always runs one chain per lane and is
+measured once per batch.  Every cell is warmed up, then timed `--repeats`
+times over `--iters` launches each (host clock around a device
+synchronise); min / median / max of the repeats are printed.
 """
+import argparse
+import statistics
 import sys
 import time
 
@@ -9,39 +21,78 @@ sys.path.insert(0, __file__.rsplit("/", 2)[0])
 import torch
 
 from llmd_kvcache_amd.ops import cpu_ext
+from llmd_kvcache_amd.utils import hashing
+
+
+def _ints(s):
+    return tuple(int(x) for x in s.split(",") if x)
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--algo", default="fnv-64a",
+                    help="comma-separated hash_algo names "
+                         f"({', '.join(hashing.NATIVE_ALGO_IDS)})")
+    ap.add_argument("--batches", type=_ints,
+                    default=(512, 1024, 2048, 4096, 8192, 16384))
+    ap.add_argument("--ilp", type=_ints, default=(1, 9, 2, 4),
+                    help="FNV ILP variants to try (SHA ignores it)")
+    ap.add_argument("--chunks", type=int, default=512,
+                    help="chunks per prompt (8k tokens / bs 16)")
+    ap.add_argument("--block-size", type=int, default=16)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=1)
+    args = ap.parse_args()
+
+    algos = [a for a in args.algo.split(",") if a]
+    for a in algos:
+        if a not in hashing.NATIVE_ALGO_IDS:
+            ap.error(f"unknown --algo {a!r}")
     mod = cpu_ext.require()
-    K = 512  # chunks per prompt (8k tokens / bs 16)
-    BS = 16
+    K = args.chunks
+    BS = args.block_size
     results = []
-    for B in (512, 1024, 2048, 4096, 8192, 16384):
+    for B in args.batches:
         toks = torch.randint(0, 1 << 31, (K * BS, B), dtype=torch.int32,
                              device="cuda")
-        parents = torch.full((B,), -3750763034362895579, dtype=torch.int64,
-                             device="cuda")  # init_hash("") as i64
         nch = torch.full((B,), K, dtype=torch.int32, device="cuda")
-        for ilp in (1, 9, 2, 4):
-            if B // ilp < 64:
-                continue
-            mod.gpu_hash_chain_tr(toks, parents, nch, BS, K, ilp)  # warmup
-            torch.cuda.synchronize()
-            t0 = time.monotonic()
-            iters = 5
-            for _ in range(iters):
-                mod.gpu_hash_chain_tr(toks, parents, nch, BS, K, ilp)
-            torch.cuda.synchronize()
-            dt = (time.monotonic() - t0) / iters
-            results.append((B, ilp, dt * 1e3, B / dt))
-            print(f"B={B:6d} ilp={ilp} {dt*1e3:8.3f} ms  "
-                  f"{B/dt/1e6:8.3f} M prompts/s  "
-                  f"{B*K/dt/1e9:6.2f} G chunks/s", flush=True)
+        for algo in algos:
+            algo_id = hashing.NATIVE_ALGO_IDS[algo]
+            init = hashing.CHAIN_ALGOS[algo][1]("")
+            parents = torch.full(
+                (B,), init - (1 << 64) if init >= (1 << 63) else init,
+                dtype=torch.int64, device="cuda")
+            for ilp in (args.ilp if algo_id == 0 else (1,)):
+                if B // ilp < 64:
+                    continue
+
+                def call():
+                    return mod.gpu_hash_chain_tr(toks, parents, nch, BS, K,
+                                                 ilp, 0, algo_id)
+
+                call()  # warmup
+                torch.cuda.synchronize()
+                times = []
+                for _ in range(args.repeats):
+                    t0 = time.monotonic()
+                    for _ in range(args.iters):
+                        call()
+                    torch.cuda.synchronize()
+                    times.append((time.monotonic() - t0) / args.iters)
+                dt = statistics.median(times)
+                results.append((B, algo, ilp, dt * 1e3, B / dt))
+                print(f"B={B:6d} algo={algo} ilp={ilp} {dt*1e3:8.3f} ms "
+                      f"(min {min(times)*1e3:.3f} max {max(times)*1e3:.3f}, "
+                      f"n={len(times)})  "
+                      f"{B/dt/1e6:8.3f} M prompts/s  "
+                      f"{B*K/dt/1e9:6.2f} G chunks/s", flush=True)
     best = {}
-    for B, ilp, ms, qps in results:
-        if B not in best or qps > best[B][1]:
-            best[B] = (ilp, qps)
-    print("best ILP per batch:", {b: v[0] for b, v in sorted(best.items())})
+    for B, algo, ilp, ms, qps in results:
+        k = (B, algo)
+        if k not in best or qps > best[k][1]:
+            best[k] = (ilp, qps)
+    print("best ILP per (batch, algo):",
+          {k: v[0] for k, v in sorted(best.items())})
 
 
 if __name__ == "__main__":
