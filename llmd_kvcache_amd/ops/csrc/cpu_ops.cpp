@@ -246,7 +246,9 @@ std::vector<uint64_t> tokens_to_chunk_hashes_fast(
     for (int64_t c = 0; c < n_chunks; ++c) {
       const uint32_t* t = toks.data() + c * block_size;
       if constexpr (decltype(A)::value == ALGO_FNV64A) {
-        h = chunk_hash_fast(h, t, (int)block_size);
+        // the wide-parent path whenever it applies, as a wave of the
+        // kernel whose parents are all wide takes it
+        h = chunk_hash_fast(h, t, (int)block_size, h > 0xFFFFFFFFull);
       } else {
         ShaHostBuf buf{words.data()};
         h = chunk_hash_sha256_wave(h, t, (int)block_size,

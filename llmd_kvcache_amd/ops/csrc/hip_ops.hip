@@ -473,11 +473,16 @@ __global__ void k_hash_chain(const int64_t* __restrict__ tokens,
 // out is [max_chunks][B] (transposed too; callers transpose back with a
 // cheap torch op or consume the stride directly).
 // ILP chains: each lane advances ILP independent prompt chains in one
-// straight-line (branchless chunk_hash_fast) loop body, so the scheduler
-// interleaves their serial FNV dependency chains - the chain is
-// dependent-ALU-latency-bound at 1 wave/SIMD, and ILP-x recovers ~x of
-// that latency.  Lane l of the grid owns prompts {l, l+L, .., l+(ILP-1)L}
-// where L = total lanes, keeping every token load coalesced.
+// straight-line (branchless chunk_hash_fast) loop body.  Measured, this
+// does not pay: with one wave per SIMD the wave is instruction-ISSUE
+// bound (one vector instruction per ~5 cycles, dependent or not), so
+// ILP-x issues x times the instructions in nearly x times the time
+// (profiles/r01_chain_sweep.md, profiles/r04_fnv_chain.md).  What makes
+// a call faster is fewer instructions per chunk; ILP 1 is the default.
+// Lane l of the grid owns prompts {l, l+L, .., l+(ILP-1)L} where
+// L = total lanes, keeping every token load coalesced.
+// The kernel writes EVERY slot of out for its prompts, a zero where
+// c >= n_chunks[b], so the caller need not clear the buffer first.
 //
 // SHA-256 policy (ALGO 1/2, ILP 1): not a re-skin of the FNV body.  FNV
 // streams bytes through one 64-bit register; SHA-256 needs 16-word
@@ -523,7 +528,8 @@ __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
     uint64_t h = parents[bi];
     const int mc = live ? n_chunks[bi] : 0;
     ShaLdsCol<NT> col{sha_words + threadIdx.x};
-    for (int c = 0; c < max_chunks; ++c) {
+    int c = 0;
+    for (; c < max_chunks; ++c) {
       const bool active = c < mc;
       if (!__any(active)) break;  // wave-uniform: chains only get shorter
       uint32_t tok[BS];
@@ -533,22 +539,28 @@ __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
       const uint64_t h2 = chunk_hash_sha256_wave(
           h, tok, BS, sha_digest_word(ALGO), col, active, ShaWaveAny{});
       h = active ? h2 : h;
-      if (active)
+      if (live)
         out[row_major ? (int64_t)lane * max_chunks + c
-                      : (int64_t)c * B + lane] = h;
+                      : (int64_t)c * B + lane] = active ? h : 0;
     }
+    // the wave left early: its remaining slots are all unused
+    if (live)
+      for (; c < max_chunks; ++c)
+        out[row_major ? (int64_t)lane * max_chunks + c
+                      : (int64_t)c * B + lane] = 0;
     return;
   }
   const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= L) return;
   int64_t b[ILP];
   uint64_t h[ILP];
   int mc[ILP];
   bool live[ILP];
+  // no early return here either: the wide-parent vote below needs whole
+  // waves, so lanes past L ride along like dead chains
 #pragma unroll
   for (int i = 0; i < ILP; ++i) {
     b[i] = lane + (int64_t)i * L;
-    live[i] = b[i] < B;
+    live[i] = lane < L && b[i] < B;
     h[i] = live[i] ? parents[b[i]] : 0;
     mc[i] = live[i] ? n_chunks[b[i]] : 0;
   }
@@ -567,15 +579,24 @@ __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
 #pragma unroll
     for (int i = 0; i < ILP; ++i) {
       const bool active = live[i] && c < mc[i];
-      const uint64_t h2 = chunk_hash_fast(h[i], tok[i], BS);
+      // Wave-uniform vote: every chain of the wave that still runs has a
+      // parent above 0xFFFFFFFF (after chunk 0 it is a 64-bit hash), so
+      // the parent item needs no selects.  A scalar branch, taken by the
+      // whole wave.  The ILP > 1 bodies stay one basic block and keep
+      // the generic parent item.
+      bool wide = false;
+      if constexpr (ILP == 1)
+        wide = __all(!active || h[i] > 0xFFFFFFFFull);
+      const uint64_t h2 = chunk_hash_fast(h[i], tok[i], BS, wide);
       h[i] = active ? h2 : h[i];
       // row_major writes land scattered (stride maxC per lane) but the
-      // kernel is ALU-latency bound with idle bandwidth - writing the
-      // layout the fused-score kernel consumes saves a 128 MB/call
-      // transpose pass downstream.
-      if (active)
+      // kernel is instruction-issue bound with idle bandwidth - writing
+      // the layout the fused-score kernel consumes saves a 128 MB/call
+      // transpose pass downstream.  Unused slots get their zero here:
+      // the caller hands in uninitialised memory.
+      if (live[i])
         out[row_major ? (int64_t)b[i] * max_chunks + c
-                      : (int64_t)c * B + b[i]] = h[i];
+                      : (int64_t)c * B + b[i]] = active ? h[i] : 0;
     }
   }
 }
@@ -609,9 +630,8 @@ __global__ void k_hash_chain_tr_pf(const int32_t* __restrict__ tokens_t,
     const bool active = c < mc;
     const uint64_t h2 = chunk_hash_fast(h, cur, BS);
     h = active ? h2 : h;
-    if (active)
-      out[row_major ? (int64_t)lane * max_chunks + c
-                    : (int64_t)c * B + lane] = h;
+    out[row_major ? (int64_t)lane * max_chunks + c
+                  : (int64_t)c * B + lane] = active ? h : 0;
 #pragma unroll
     for (int j = 0; j < BS; ++j) cur[j] = nxt[j];
   }
@@ -1141,16 +1161,23 @@ at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
   TORCH_CHECK(parents.numel() == B && n_chunks.numel() == B);
   // row_major=1: out is [B, max_chunks] (what the fused-score kernel
   // consumes directly - no transpose pass); default [max_chunks, B].
-  auto out = at::zeros(row_major ? std::initializer_list<int64_t>{B, max_chunks}
+  // Not cleared: the kernels write every slot, a zero where
+  // c >= n_chunks[b].  Keep it so.  A fill kernel in front of the chain
+  // call costs only tens of µs, but with two kernels per call on the
+  // read path's side stream the runtime keeps falling back to running
+  // that stream and the score stream one after the other (call time
+  // 1.2 -> 2.7 ms, flipping between and within processes; measured
+  // with only this line changed, profiles/r04_fnv_chain.md).
+  auto out = at::empty(row_major ? std::initializer_list<int64_t>{B, max_chunks}
                                  : std::initializer_list<int64_t>{max_chunks, B},
                        parents.options());
   if (B == 0 || max_chunks == 0) return out;
+  TORCH_CHECK(tokens_t.size(0) >= max_chunks * block_size,
+              "tokens_t has fewer rows than max_chunks * block_size");
+  auto tokens_c = tokens_t.contiguous();
   if (algo != ALGO_FNV64A) {
     // SHA-256 chains: one prompt per lane (ilp is an FNV tuning knob and
     // is ignored), workgroup width set by the LDS payload columns.
-    TORCH_CHECK(tokens_t.size(0) >= max_chunks * block_size,
-                "tokens_t has fewer rows than max_chunks * block_size");
-    auto tokens_c = tokens_t.contiguous();
     auto launch_sha = [&](auto kern, int threads) {
       int blocks = (int)((B + threads - 1) / threads);
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, STREAM,
@@ -1177,20 +1204,26 @@ at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
     });
     return out;
   }
-  // ILP trades wave count for per-lane chain interleave: only pay the
-  // wave reduction when there are waves to spare (tuned by
-  // scripts/sweep_chain.py on MI355X).
+  // ILP puts several chains on one lane.  Sweep on MI355X
+  // (profiles/r01_chain_sweep.md): ILP>1 always loses - a lone wave is
+  // issue-bound, so x chains per lane cost close to x times the time
+  // whether or not they interleave.  Default 1.
   int64_t want_ilp = ilp;
-  // Sweep on MI355X (profiles/r01_chain_sweep.md): ILP>1 always loses -
-  // register pressure + extra loads outweigh the interleave; the
-  // branchless body alone keeps the SIMD pipeline fed.  Default 1.
   if (want_ilp <= 0) want_ilp = 1;
   int64_t L = (B + want_ilp - 1) / want_ilp;  // lanes
-  int threads = 256;
+  // One-wave workgroups: B / 64 waves spread over all CUs before any CU
+  // gets a second one, where 256-thread workgroups put four waves on
+  // each of a quarter as many CUs.  Measured (profiles/r04_fnv_chain.md):
+  // alone, the row-major call is 8 % shorter and the transposed one the
+  // same; beside the score kernel the chain gains what the score kernel
+  // loses, and the chain is the longer stream, so the read call gets
+  // shorter.  A raised wave priority (s_setprio 1 at kernel entry) was
+  // tried with either shape and changed nothing measurable.
+  int threads = 64;
   int blocks = (int)((L + threads - 1) / threads);
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, STREAM,
-                       tokens_t.data_ptr<int32_t>(), U64P(parents),
+                       tokens_c.data_ptr<int32_t>(), U64P(parents),
                        n_chunks.data_ptr<int32_t>(), B, L, (int)max_chunks,
                        (int)row_major,
                        reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));

@@ -123,25 +123,31 @@ KVIDX_HD uint64_t fnv_cbor_uint(uint64_t h, uint64_t v, uint8_t major) {
 }
 
 // Branchless (predicated) variants: identical output to fnv_cbor_uint but
-// straight-line code - on the GPU this lets the scheduler interleave
-// several independent chains' instruction streams (ILP hash kernels) and
-// removes lane divergence on data-dependent encoding lengths.
+// straight-line code, so lanes of a wave never diverge on the
+// data-dependent encoding lengths.  One wave alone on a SIMD is
+// issue-bound (about 5 cycles per vector instruction whatever it is), so
+// what counts here is the number of instructions, not their latency:
+//  - a u32 has 0, 1, 2 or 4 value bytes, never 3, so the two high bytes
+//    share one predicate and run back to back under ONE 64-bit select;
+//  - all three predicates and the header byte depend on v alone and are
+//    computed ahead of the first step, which leaves the compiler free to
+//    place each compare well before the select that reads it (a compare
+//    directly in front of its select costs a hazard nop).
 KVIDX_HD uint64_t fnv_cbor_u32_branchless(uint64_t h, uint32_t v,
                                           uint8_t major) {
   const uint8_t mt = major << 5;
-  const int sel = (v >= 24) + (v > 0xFF) + (v > 0xFFFF);  // 0..3
-  const int n = sel == 3 ? 4 : sel;  // value bytes
-  const uint8_t header = sel ? (uint8_t)(mt | (0x17 + sel))
-                             : (uint8_t)(mt | v);
-  h = fnv1a_64_byte(h, header);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-  for (int k = 0; k < 4; ++k) {
-    const uint8_t b = (uint8_t)(v >> (8 * (3 - k)));
-    const uint64_t h2 = fnv1a_64_byte(h, b);
-    h = (k >= 4 - n) ? h2 : h;
-  }
+  const bool p1 = v >= 24;      // at least one value byte
+  const bool p2 = v > 0xFF;     // at least two
+  const bool p4 = v > 0xFFFF;   // four
+  const uint8_t info = p4 ? 26 : p2 ? 25 : p1 ? 24 : (uint8_t)v;
+  h = fnv1a_64_byte(h, (uint8_t)(mt | info));
+  const uint64_t h4 = fnv1a_64_byte(fnv1a_64_byte(h, (uint8_t)(v >> 24)),
+                                    (uint8_t)(v >> 16));
+  h = p4 ? h4 : h;
+  const uint64_t h2 = fnv1a_64_byte(h, (uint8_t)(v >> 8));
+  h = p2 ? h2 : h;
+  const uint64_t h1 = fnv1a_64_byte(h, (uint8_t)v);
+  h = p1 ? h1 : h;
   return h;
 }
 
@@ -165,17 +171,42 @@ KVIDX_HD uint64_t fnv_cbor_u64_branchless(uint64_t h, uint64_t v,
   return h;
 }
 
+// A uint above 0xFFFFFFFF: header 0x1B (major 0) and eight value bytes,
+// nothing to select.  The caller guarantees the range.
+KVIDX_HD uint64_t fnv_cbor_u64_wide(uint64_t h, uint64_t v) {
+  h = fnv1a_64_byte(h, 0x1B);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int s = 56; s >= 0; s -= 8) h = fnv1a_64_byte(h, (uint8_t)(v >> s));
+  return h;
+}
+
 // Branchless chain link (bit-identical to chunk_hash; GPU hot path).
 // The token loop is force-unrolled on device: a rolled loop makes hipcc
 // read tok[] via gpr_idx (register-indexed) with a vmcnt(0) wait at the
 // loop head, which both serializes the reads and drains any prefetched
 // next-chunk loads (measured in the k_hash_chain_tr ISA).
+//
+// wide_parent: the caller promises parent > 0xFFFFFFFF, which a chained
+// parent (a 64-bit hash) is with probability 1 - 2^-32; the parent item
+// is then nine straight steps in place of eight predicated ones.  On the
+// device the flag must be uniform over the wave (k_hash_chain_tr votes
+// on it) so that taking it is a scalar branch.  Callers that run one
+// chain on a single lane or per-lane event chains (the ingest kernels)
+// pass false: they have no whole wave to vote with, and a per-lane
+// branch would make the wave run both bodies.  Everything after the
+// parent item is the same code either way.
 template <typename TokT>
 KVIDX_HD uint64_t chunk_hash_fast(uint64_t parent, const TokT* tokens,
-                                  int n) {
+                                  int n, bool wide_parent = false) {
   uint64_t h = FNV64_OFFSET;
   h = fnv1a_64_byte(h, 0x83);
-  h = fnv_cbor_u64_branchless(h, parent, 0);
+  if (wide_parent)
+    h = fnv_cbor_u64_wide(h, parent);
+  else
+    h = fnv_cbor_u64_branchless(h, parent, 0);
+  // for a compile-time n the array header folds to constant bytes
   h = fnv_cbor_u32_branchless(h, (uint32_t)n, 4);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
