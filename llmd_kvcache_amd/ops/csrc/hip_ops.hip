@@ -509,6 +509,15 @@ constexpr int sha_tr_words(int bs) {
   return 16 * sha_blocks_for(sha_max_payload(bs));
 }
 
+// Row-major staging of the FNV ILP-1 chain (see the kernel): chunks per
+// flush, u64 per staged prompt row (one pad), dynamic LDS per workgroup.
+constexpr int CHAIN_STAGE_CHUNKS = 16;
+constexpr int CHAIN_STAGE_ROW = CHAIN_STAGE_CHUNKS + 1;
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+constexpr size_t chain_stage_bytes(int threads) {
+  return (size_t)threads * CHAIN_STAGE_ROW * sizeof(uint64_t);
+}
+
 template <int BS, int ILP, int ALGO = ALGO_FNV64A>
 __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
                                 const uint64_t* __restrict__ parents,  // [B]
@@ -551,6 +560,27 @@ __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
     return;
   }
   const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // Row-major output, ILP 1: a store of one chunk's hashes straight from
+  // the lanes is 64 separate 8-byte pieces, max_chunks * 8 bytes apart.
+  // The wave parks each chunk's hashes in LDS instead and, every
+  // CHAIN_STAGE_CHUNKS chunks, writes each prompt's 128 bytes as eight
+  // 16-byte stores from eight neighbouring lanes: whole lines.
+  // Layout [prompt][17] u64 (16 chunks + 1 pad, 136 B rows), by the LDS
+  // bank model (ds_write_b64 and ds_read2_b64: bank = dword address mod
+  // 32, conflicts within groups of 16 consecutive lanes):
+  //  - write, lane p stores dwords 34p+2cc, +1: 34 = 2 mod 32, so 16
+  //    lanes cover all 32 banks once;
+  //  - read, lane l takes dwords 34(8g + l/8) + 4(l%8) + {0,1} and
+  //    {2,3}: per access the 8 lanes of a row hit banks 4i, 4i+1 off the
+  //    row's base, the group's other row is based 2 banks further on and
+  //    fills the gaps.
+  // Both are conflict-free.  One wave owns its region, and a wave's LDS
+  // operations execute in order, so wavefront-scope fences (no
+  // instructions, only compiler ordering) are all the synchronisation.
+  extern __shared__ uint64_t chain_stage[];  // [waves][64][CHAIN_STAGE_ROW]
+  const int wl = threadIdx.x & 63;
+  uint64_t* stage =
+      chain_stage + (size_t)(threadIdx.x >> 6) * (64 * CHAIN_STAGE_ROW);
   int64_t b[ILP];
   uint64_t h[ILP];
   int mc[ILP];
@@ -589,14 +619,54 @@ __global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
         wide = __all(!active || h[i] > 0xFFFFFFFFull);
       const uint64_t h2 = chunk_hash_fast(h[i], tok[i], BS, wide);
       h[i] = active ? h2 : h[i];
-      // row_major writes land scattered (stride maxC per lane) but the
-      // kernel is instruction-issue bound with idle bandwidth - writing
-      // the layout the fused-score kernel consumes saves a 128 MB/call
-      // transpose pass downstream.  Unused slots get their zero here:
-      // the caller hands in uninitialised memory.
-      if (live[i])
+      // row_major writes the layout the fused-score kernel consumes,
+      // which saves a 128 MB/call transpose pass downstream.  Unused
+      // slots get their zero here: the caller hands in uninitialised
+      // memory.  With ILP > 1 the row-major stores stay scattered
+      // (stride maxC per lane).
+      const uint64_t val = active ? h[i] : 0;
+      if (ILP == 1 && row_major)
+        stage[wl * CHAIN_STAGE_ROW + (c & (CHAIN_STAGE_CHUNKS - 1))] = val;
+      else if (live[i])
         out[row_major ? (int64_t)b[i] * max_chunks + c
-                      : (int64_t)c * B + b[i]] = active ? h[i] : 0;
+                      : (int64_t)c * B + b[i]] = val;
+    }
+    if constexpr (ILP == 1) {
+      const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
+      if (row_major && (cc == CHAIN_STAGE_CHUNKS - 1 || c == max_chunks - 1)) {
+        // flush chunks [c0, c0 + n): lane l writes chunks c0 + 2(l%8),
+        // +1 of prompt 8g + l/8 of this wave, g = 0..7
+        const int c0 = c - cc;
+        const int n = cc + 1;
+        // rows start 16-byte aligned iff max_chunks is even; n is then
+        // even too.  Odd max_chunks keeps 8-byte stores.
+        const bool vec = (max_chunks & 1) == 0 &&
+                         (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+        const int part2 = 2 * (wl & 7);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+          const int r = g * 8 + (wl >> 3);
+          const int64_t pb = lane - wl + r;  // prompt of row r
+          const uint64_t* s = stage + r * CHAIN_STAGE_ROW + part2;
+          const uint64_t v0 = s[0];
+          const uint64_t v1 = s[1];
+          if (pb < B && part2 < n) {
+            uint64_t* o = out + pb * max_chunks + c0 + part2;
+            if (vec) {
+              *reinterpret_cast<u64x2*>(o) = u64x2{v0, v1};  // dwordx4
+            } else {
+              o[0] = v0;
+              if (part2 + 1 < n) o[1] = v1;
+            }
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
     }
   }
 }
@@ -1218,11 +1288,14 @@ at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
   // same; beside the score kernel the chain gains what the score kernel
   // loses, and the chain is the longer stream, so the read call gets
   // shorter.  A raised wave priority (s_setprio 1 at kernel entry) was
-  // tried with either shape and changed nothing measurable.
+  // tried with either shape and changed nothing measurable.  Measured
+  // again with row-major output staged through LDS
+  // (profiles/r05_score_walk.md): the two widths give the same call
+  // time, 64 is 0.005..0.008 ms shorter alone; 64 stays.
   int threads = 64;
   int blocks = (int)((L + threads - 1) / threads);
-  auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, STREAM,
+  auto launch = [&](auto kern, size_t lds = 0) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, STREAM,
                        tokens_c.data_ptr<int32_t>(), U64P(parents),
                        n_chunks.data_ptr<int32_t>(), B, L, (int)max_chunks,
                        (int)row_major,
@@ -1246,7 +1319,10 @@ at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
         launch(k_hash_chain_tr_pf<16>);
         break;
       case 4: launch(k_hash_chain_tr<16, 4>); break;
-      default: launch(k_hash_chain_tr<16, 1>); break;
+      default:  // the read path's kernel; row-major output stages in LDS
+        launch(k_hash_chain_tr<16, 1>,
+               row_major ? chain_stage_bytes(threads) : 0);
+        break;
     }
   }
   if (!done) {
