@@ -48,9 +48,59 @@ class Config:
     backend_configs: List[KVCacheBackendConfig] = field(
         default_factory=default_kv_cache_backend_configs
     )
+    # Read-path route of score_flat_tokens on a GPU table (see
+    # plan_read_route): "off" chains on the CPU and uploads the hashes,
+    # "on" uploads the raw tokens and chains on the GPU whenever that is
+    # possible, "auto" does so from device_chain_min_chunks total chunks
+    # per batch on.  8192 is the measured crossover of the two routes
+    # (fnv-64a 6123 chunks, sha256-cbor-64 14776; 1024..8192-token
+    # prompts, profiles/r06_device_read_path.md).
+    device_chain: str = "auto"
+    device_chain_min_chunks: int = 8192
+    # a batch whose padded token image B * max_k * block_size * 4 bytes
+    # exceeds this stays on the CPU chain (one very long prompt among
+    # thousands of short ones)
+    device_chain_max_image_bytes: int = 1 << 30
 
 
 _log = get_logger("indexer")
+
+DEVICE_CHAIN_BLOCK_SIZES = (4, 8, 16, 32, 64)
+
+
+@dataclass
+class ReadRoute:
+    device: bool        # True: gpu_score_flat_tokens; False: CPU chain
+    n_chunks: List[int]  # whole chunks per prompt
+    max_k: int
+    image_bytes: int    # padded int32 token image of the device route
+
+
+def plan_read_route(offsets, block_size: int, hash_algo: str,
+                    table_on_gpu: bool, config: Config) -> ReadRoute:
+    """Which way a batch takes through score_flat_tokens.  Pure: no
+    tensors are touched beyond reading the offsets.  The device route is
+    taken only where it is possible (GPU table, native algo, a block size
+    the transposed chain kernel has, image under the cap) and wanted
+    ("on", or "auto" at or above the threshold); everything else takes
+    the CPU chain."""
+    off = offsets.tolist() if hasattr(offsets, "tolist") else list(offsets)
+    n_chunks = [(int(off[i + 1]) - int(off[i])) // block_size
+                for i in range(len(off) - 1)]
+    max_k = max(n_chunks, default=0)
+    image_bytes = len(n_chunks) * max_k * block_size * 4
+    route = ReadRoute(False, n_chunks, max_k, image_bytes)
+    mode = config.device_chain
+    if mode not in ("auto", "on"):
+        return route
+    if not (table_on_gpu and hash_algo in hashing.NATIVE_ALGO_IDS
+            and block_size in DEVICE_CHAIN_BLOCK_SIZES
+            and image_bytes <= config.device_chain_max_image_bytes):
+        return route
+    if mode == "auto" and sum(n_chunks) < config.device_chain_min_chunks:
+        return route
+    route.device = True
+    return route
 
 
 class Indexer:
@@ -216,9 +266,9 @@ class Indexer:
         pod_identifiers: Sequence[str],
     ):
         """Core batched scorer over flat int64 token tensors: parallel
-        C++ chain -> one fused probe/score.  Returns the [B, num_pods]
-        float32 score tensor (CPU or device).  This is the entry the C++
-        wirefront calls once per micro-batch."""
+        C++ chain -> one fused probe/score, or on a GPU table, where
+        plan_read_route says so, the chain on the device as well.
+        Returns the [B, num_pods] float32 score tensor (CPU or device)."""
         import torch
 
         from .kvblock.gpu_index import _to_i64
@@ -228,6 +278,21 @@ class Indexer:
         bs = tp.block_size
         B = int(offsets.numel()) - 1
         init = _to_i64(tp.config.init_hash())
+        route = plan_read_route(offsets, bs, tp.config.hash_algo,
+                                idx.table.is_cuda, self.config)
+        if route.device and route.max_k > 0:
+            # raw tokens up, chain + probe + walk on the device: same
+            # chain function, same walk, the same scores bit for bit
+            num_pods = idx._num_pods_padded()
+            return idx.table.ops.gpu_score_flat_tokens(
+                *idx.table._t(), tokens_flat, offsets,
+                idx.registry.model_id(model_name),
+                idx._filter_tensor(set(pod_identifiers), num_pods),
+                idx.tier_weights(
+                    {b.name: b.weight for b in self.config.backend_configs}),
+                num_pods, idx.table.next_epoch(), init, bs,
+                max(1, len(idx.registry.id_to_tier)),
+                hashing.NATIVE_ALGO_IDS[tp.config.hash_algo])
         parents = torch.full((B,), init, dtype=torch.int64)
         hashes, chunk_off = idx.table.ops.hash_chain_batch(
             tokens_flat, offsets, parents, bs,

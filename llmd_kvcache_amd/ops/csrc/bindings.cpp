@@ -70,6 +70,18 @@ std::vector<at::Tensor> gpu_hash_chain(at::Tensor, at::Tensor, at::Tensor,
                                        int64_t, int64_t);
 at::Tensor gpu_hash_chain_tr(at::Tensor, at::Tensor, at::Tensor, int64_t,
                              int64_t, int64_t, int64_t, int64_t);
+at::Tensor gpu_fused_score_rows(at::Tensor, at::Tensor, at::Tensor,
+                                at::Tensor, at::Tensor, at::Tensor,
+                                at::Tensor, int64_t, at::Tensor, at::Tensor,
+                                int64_t, at::Tensor, at::Tensor, int64_t,
+                                int64_t, int64_t, int64_t);
+std::vector<at::Tensor> gpu_stage_ragged_tokens(at::Tensor, at::Tensor,
+                                                int64_t);
+at::Tensor gpu_score_flat_tokens(at::Tensor, at::Tensor, at::Tensor,
+                                 at::Tensor, at::Tensor, at::Tensor,
+                                 at::Tensor, int64_t, at::Tensor, at::Tensor,
+                                 int64_t, at::Tensor, at::Tensor, int64_t,
+                                 int64_t, int64_t, int64_t, int64_t, int64_t);
 void gpu_apply_events(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, int64_t, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, at::Tensor,
@@ -132,6 +144,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tokens_t"), py::arg("parents"), py::arg("n_chunks"),
         py::arg("block_size"), py::arg("max_chunks"), py::arg("ilp") = 0,
         py::arg("row_major") = 0, py::arg("algo") = 0);
+  m.def("gpu_fused_score_rows", &kvidx::gpu_fused_score_rows);
+  m.def("gpu_stage_ragged_tokens", &kvidx::gpu_stage_ragged_tokens,
+        py::arg("tokens"), py::arg("offsets"), py::arg("block_size"));
+  // stage + chain + score in one call; the GIL is released for all of it
+  m.def("gpu_score_flat_tokens", &kvidx::gpu_score_flat_tokens,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("offsets"),
+        py::arg("model_id"), py::arg("filter_words"), py::arg("weights"),
+        py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("n_tiers"), py::arg("algo") = 0,
+        py::call_guard<py::gil_scoped_release>());
   m.def("gpu_apply_events", &kvidx::gpu_apply_events,
         py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
         py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),

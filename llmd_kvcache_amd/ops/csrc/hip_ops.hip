@@ -330,9 +330,13 @@ __global__ void k_lookup_masks(DevTable v, const uint64_t* __restrict__ rh,
 // Fused probe + longest-prefix score. One workgroup per prompt; dynamic
 // LDS holds the per-key per-tier masks; wave 0 then walks keys in order
 // with the active pod set in registers (lane l = pod bit l).
-__global__ void __launch_bounds__(256) k_fused_score(
-    DevTable v, const uint64_t* __restrict__ hashes,
-    const int32_t* __restrict__ offsets,  // [B+1]
+//
+// The body is shared by two entries that differ only in where prompt b's
+// keys lie: k_fused_score takes flat hashes with offsets [B+1],
+// k_fused_score_rows takes padded rows (h = hashes + b * stride, K =
+// n_keys[b]) as the row-major chain kernel leaves them.
+DEV void fused_score_body(
+    DevTable v, const uint64_t* __restrict__ h, const int K,
     uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
     const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
     int n_tiers, float* __restrict__ scores) {
@@ -341,8 +345,6 @@ __global__ void __launch_bounds__(256) k_fused_score(
   // at 16-32 KB/WG instead of 64 KB, preserving occupancy.
   extern __shared__ unsigned long long lds_masks[];  // [K, n_tiers, W]
   const int b = blockIdx.x;
-  const int K = offsets[b + 1] - offsets[b];
-  const uint64_t* h = hashes + offsets[b];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
 
@@ -390,6 +392,32 @@ __global__ void __launch_bounds__(256) k_fused_score(
     int pid = w * 64 + lane;
     if (pid < num_pods) scores[(size_t)b * num_pods + pid] = score;
   }
+}
+
+__global__ void __launch_bounds__(256) k_fused_score(
+    DevTable v, const uint64_t* __restrict__ hashes,
+    const int32_t* __restrict__ offsets,  // [B+1]
+    uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
+    const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
+    int n_tiers, float* __restrict__ scores) {
+  const int b = blockIdx.x;
+  fused_score_body(v, hashes + offsets[b], offsets[b + 1] - offsets[b], model,
+                   filter, has_filter, weights, num_pods, W, epoch, n_tiers,
+                   scores);
+}
+
+// Padded rows: prompt b's keys are hashes[b * stride .. + n_keys[b]).  The
+// slots past n_keys[b] are never read (the chain kernel zeroes them, and
+// remap_hash(0) is a legal key).
+__global__ void __launch_bounds__(256) k_fused_score_rows(
+    DevTable v, const uint64_t* __restrict__ hashes,  // [B, stride]
+    const int32_t* __restrict__ n_keys,               // [B]
+    int64_t stride, uint32_t model, const uint64_t* __restrict__ filter,
+    int has_filter, const float* __restrict__ weights, int num_pods, int W,
+    int32_t epoch, int n_tiers, float* __restrict__ scores) {
+  const int b = blockIdx.x;
+  fused_score_body(v, hashes + (int64_t)b * stride, n_keys[b], model, filter,
+                   has_filter, weights, num_pods, W, epoch, n_tiers, scores);
 }
 
 // Walk precomputed masks (e.g. after an RCCL all-reduce merge of shard
@@ -912,6 +940,65 @@ __global__ void k_transpose_ev_tokens(const int32_t* __restrict__ flat,
     out[(int64_t)i * E + e] = flat[tok_off[e] + i];
 }
 
+// Read-path staging for k_hash_chain_tr: flat ragged tokens (int64 or
+// int32, narrowed to their low 32 bits as hash_chain_batch does) ->
+// transposed int32 image [T = max_chunks * block_size][B].  A read batch
+// is ~128 MB of image (4096 prompts x 8192 tokens), so unlike the event
+// transpose above it goes through LDS: a workgroup moves one tile of 64
+// prompts x 64 positions, reading 64 consecutive positions of a prompt
+// per wave (one contiguous 512 B / 256 B piece) and writing one position
+// of 64 consecutive prompts per wave (one 256 B line).
+// LDS int32 [64][65].  ds_write_b32 / ds_read_b32: bank = dword address
+// mod 32, conflicts within a 32-lane half.  The write of row r puts lane
+// l at dword 65 r + l: consecutive.  The read of column r takes lane l
+// from dword 65 l + r, and 65 = 1 mod 32: a half covers the 32 banks
+// once.  Both are conflict-free.
+// Every slot of the image is written, a zero at and past a prompt's last
+// whole chunk and in the positions of short prompts, so the caller hands
+// in uninitialised memory (the chain kernels load all T rows for every
+// lane).  Grid = (ceil(T / 64), ceil(B / 64)).
+constexpr int STAGE_TILE = 64;
+template <typename TokT>
+__global__ void __launch_bounds__(256) k_stage_ragged_tokens(
+    const TokT* __restrict__ flat,          // [total]
+    const int32_t* __restrict__ tok_off,    // [B+1]
+    const int32_t* __restrict__ n_chunks,   // [B]
+    int64_t B, int64_t T, int block_size,
+    int32_t* __restrict__ out) {            // [T, B]
+  __shared__ int32_t tile[STAGE_TILE][STAGE_TILE + 1];
+  const int lane = threadIdx.x & 63;
+  // the wave's index as a scalar, so that what depends on the prompt alone
+  // (its offset and length) is loaded and computed once per wave
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t t0 = (int64_t)blockIdx.x * STAGE_TILE;
+  const int64_t p0 = (int64_t)blockIdx.y * STAGE_TILE;
+  constexpr int ROWS = STAGE_TILE / 4;  // tile rows per wave
+  const int64_t pos = t0 + lane;
+  // Unconditional loads from clamped addresses (token 0 exists: T > 0),
+  // then selects: no branch, so the 16 loads of a lane are all in flight
+  // before the first LDS write waits for its own.
+  int32_t x[ROWS];
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) {
+    const int r = wave + 4 * i;
+    const int64_t b = min(p0 + r, B - 1);
+    const int64_t keep = (int64_t)n_chunks[b] * block_size;
+    const int64_t first = tok_off[b];
+    const bool ok = p0 + r < B && pos < keep;
+    const int32_t v = (int32_t)flat[ok ? first + pos : 0];
+    x[i] = ok ? v : 0;
+  }
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) tile[wave + 4 * i][lane] = x[i];
+  __syncthreads();
+  const int64_t b = p0 + lane;
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) {
+    const int r = wave + 4 * i;
+    if (t0 + r < T && b < B) out[(t0 + r) * B + b] = tile[lane][r];
+  }
+}
+
 template <int ALGO>
 __global__ void k_event_chains_ev(
     DevTable v, const int32_t* __restrict__ tokens_t,  // [maxT, E]
@@ -1340,6 +1427,191 @@ at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
     }
   }
   return out;
+}
+
+// gpu_fused_score over the padded rows that gpu_hash_chain_tr(row_major=1)
+// returns: hashes int64 [B, stride], n_keys int32 [B] on the device.
+at::Tensor gpu_fused_score_rows(at::Tensor keys, at::Tensor meta,
+                                at::Tensor stamp, at::Tensor pods,
+                                at::Tensor e_keys, at::Tensor e_meta,
+                                at::Tensor e_vals, int64_t pods_per_key,
+                                at::Tensor hashes, at::Tensor n_keys,
+                                int64_t model_id, at::Tensor filter_words,
+                                at::Tensor weights, int64_t num_pods,
+                                int64_t epoch, int64_t max_k,
+                                int64_t n_tiers) {
+  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
+                    pods_per_key);
+  TORCH_CHECK(hashes.is_cuda() && hashes.dtype() == at::kLong &&
+                  hashes.dim() == 2 && hashes.is_contiguous(),
+              "hashes must be a contiguous int64 [B, stride] device tensor");
+  TORCH_CHECK(n_keys.is_cuda() && n_keys.dtype() == at::kInt &&
+                  n_keys.is_contiguous(),
+              "n_keys must be a contiguous int32 device tensor");
+  int64_t B = hashes.size(0);
+  int64_t stride = hashes.size(1);
+  TORCH_CHECK(n_keys.numel() == B, "n_keys must have one entry per row");
+  TORCH_CHECK(max_k <= stride, "max_k exceeds the row length");
+  int64_t W = (num_pods + 63) / 64;
+  TORCH_CHECK(W <= 16, "fused score supports up to 1024 pods");
+  if (n_tiers < 1) n_tiers = 1;
+  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
+  size_t lds = (size_t)max_k * n_tiers * W * sizeof(uint64_t);
+  TORCH_CHECK(lds <= 64 * 1024,
+              "fused score LDS overflow: reduce keys per prompt or pods");
+  bool has_filter = filter_words.numel() > 0;
+  auto scores = at::zeros({B, num_pods},
+                          hashes.options().dtype(at::kFloat));
+  if (B == 0) return scores;
+  hipLaunchKernelGGL(
+      k_fused_score_rows, dim3((int)B), dim3(256), lds, STREAM, v,
+      U64P(hashes), n_keys.data_ptr<int32_t>(), stride, (uint32_t)model_id,
+      has_filter ? U64P(filter_words) : nullptr, has_filter ? 1 : 0,
+      weights.data_ptr<float>(), (int)num_pods, (int)W, (int32_t)epoch,
+      (int)n_tiers, scores.data_ptr<float>());
+  return scores;
+}
+
+// Host half of the ragged staging: what the offsets say about a batch.
+// One int32 buffer [n_chunks (B) | token offsets (B+1)] so that both go
+// up in one copy.
+struct RaggedPlan {
+  int64_t B = 0, max_k = 0, total_chunks = 0;
+  at::Tensor host;  // int32 [2B+1]
+};
+
+static RaggedPlan plan_ragged(const at::Tensor& tokens,
+                              const at::Tensor& offsets, int64_t block_size) {
+  TORCH_CHECK(block_size > 0, "block_size must be positive");
+  TORCH_CHECK(offsets.dtype() == at::kLong && offsets.dim() == 1 &&
+                  offsets.numel() >= 1,
+              "offsets must be an int64 [B+1] tensor");
+  TORCH_CHECK(tokens.dim() == 1 &&
+                  (tokens.dtype() == at::kLong || tokens.dtype() == at::kInt),
+              "tokens must be a flat int64 or int32 tensor");
+  auto off = offsets.to(at::kCPU).contiguous();
+  const int64_t* offp = off.data_ptr<int64_t>();
+  RaggedPlan p;
+  p.B = off.numel() - 1;
+  // the kernel trusts these: it reads tokens[off[b] + i] unchecked
+  TORCH_CHECK(offp[0] >= 0 && offp[p.B] <= tokens.numel(),
+              "offsets reach outside the token tensor");
+  TORCH_CHECK(offp[p.B] <= INT32_MAX,
+              "more than 2^31 - 1 tokens in one batch");
+  p.host = at::empty({2 * p.B + 1}, at::kInt);
+  int32_t* nc = p.host.data_ptr<int32_t>();
+  int32_t* o32 = nc + p.B;
+  for (int64_t b = 0; b < p.B; ++b) {
+    int64_t len = offp[b + 1] - offp[b];
+    TORCH_CHECK(len >= 0, "offsets must not decrease");
+    int64_t k = len / block_size;
+    nc[b] = (int32_t)k;
+    o32[b] = (int32_t)offp[b];
+    p.max_k = std::max(p.max_k, k);
+    p.total_chunks += k;
+  }
+  o32[p.B] = (int32_t)offp[p.B];
+  return p;
+}
+
+// -> {tokens_t int32 [max_k * block_size, B], n_chunks int32 [B]} on dev.
+// Host tokens go up once, unconverted; device tokens are read in place.
+static std::vector<at::Tensor> stage_ragged(const RaggedPlan& p,
+                                            at::Tensor tokens,
+                                            int64_t block_size,
+                                            at::Device dev) {
+  auto up = p.host.to(dev);
+  auto n_chunks = up.slice(0, 0, p.B);
+  auto tok_off = up.slice(0, p.B, 2 * p.B + 1);
+  int64_t T = p.max_k * block_size;
+  auto out = at::empty({T, p.B}, up.options());
+  if (p.B == 0 || T == 0) return {out, n_chunks};
+  auto tok = tokens.is_cuda() ? tokens.contiguous()
+                              : tokens.contiguous().to(dev);
+  int64_t pt = (p.B + STAGE_TILE - 1) / STAGE_TILE;
+  TORCH_CHECK(pt <= 65535, "too many prompts in one batch");
+  dim3 grid((unsigned)((T + STAGE_TILE - 1) / STAGE_TILE), (unsigned)pt);
+  if (tok.dtype() == at::kLong)
+    hipLaunchKernelGGL(k_stage_ragged_tokens<int64_t>, grid, dim3(256), 0,
+                       STREAM, tok.data_ptr<int64_t>(),
+                       tok_off.data_ptr<int32_t>(),
+                       n_chunks.data_ptr<int32_t>(), p.B, T, (int)block_size,
+                       out.data_ptr<int32_t>());
+  else
+    hipLaunchKernelGGL(k_stage_ragged_tokens<int32_t>, grid, dim3(256), 0,
+                       STREAM, tok.data_ptr<int32_t>(),
+                       tok_off.data_ptr<int32_t>(),
+                       n_chunks.data_ptr<int32_t>(), p.B, T, (int)block_size,
+                       out.data_ptr<int32_t>());
+  return {out, n_chunks};
+}
+
+std::vector<at::Tensor> gpu_stage_ragged_tokens(at::Tensor tokens,
+                                                at::Tensor offsets,
+                                                int64_t block_size) {
+  auto p = plan_ragged(tokens, offsets, block_size);
+  at::Device dev = tokens.is_cuda()
+                       ? tokens.device()
+                       : at::Device(at::kCUDA, at::cuda::current_device());
+  return stage_ragged(p, tokens, block_size, dev);
+}
+
+// The read path with the chain on the device: stage -> chain (row-major)
+// -> fused score over the padded rows, all on the current stream with no
+// host wait in between.  Returns float32 [B, num_pods] on the table's
+// device.  Scores equal hash_chain_batch + gpu_fused_score bit for bit:
+// same chain function, same walk.
+at::Tensor gpu_score_flat_tokens(at::Tensor keys, at::Tensor meta,
+                                 at::Tensor stamp, at::Tensor pods,
+                                 at::Tensor e_keys, at::Tensor e_meta,
+                                 at::Tensor e_vals, int64_t pods_per_key,
+                                 at::Tensor tokens_flat, at::Tensor offsets,
+                                 int64_t model_id, at::Tensor filter_words,
+                                 at::Tensor weights, int64_t num_pods,
+                                 int64_t epoch, int64_t init_hash_bits,
+                                 int64_t block_size, int64_t n_tiers,
+                                 int64_t algo) {
+  TORCH_CHECK(keys.is_cuda(), "table must live on the GPU");
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  auto p = plan_ragged(tokens_flat, offsets, block_size);
+  auto dev = keys.device();
+  auto fopt = at::TensorOptions().device(dev).dtype(at::kFloat);
+  if (p.B == 0 || p.max_k == 0) return at::zeros({p.B, num_pods}, fopt);
+  auto staged = stage_ragged(p, tokens_flat, block_size, dev);
+  auto parents = at::full({p.B}, init_hash_bits, fopt.dtype(at::kLong));
+  auto hashes = gpu_hash_chain_tr(staged[0], parents, staged[1], block_size,
+                                  p.max_k, 0, 1, algo);
+  if (n_tiers < 1) n_tiers = 1;
+  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
+  int64_t W = (num_pods + 63) / 64;
+  if (W <= 16 && p.max_k * n_tiers * W * 8 <= 64 * 1024)
+    return gpu_fused_score_rows(keys, meta, stamp, pods, e_keys, e_meta,
+                                e_vals, pods_per_key, hashes, staged[1],
+                                model_id, filter_words, weights, num_pods,
+                                epoch, p.max_k, n_tiers);
+  // The masks do not fit in LDS (huge fleet x long prompts; rare): gather
+  // the live slots of the rows into flat hashes and take the two-kernel
+  // path.  The gather index comes from the host's n_chunks, no wait.
+  auto idx_h = at::empty({p.total_chunks}, at::kLong);
+  auto off_h = at::empty({p.B + 1}, at::kInt);
+  {
+    const int32_t* nc = p.host.data_ptr<int32_t>();
+    int64_t* ip = idx_h.data_ptr<int64_t>();
+    int32_t* op = off_h.data_ptr<int32_t>();
+    TORCH_CHECK(p.total_chunks <= INT32_MAX, "too many chunks in one batch");
+    int64_t n = 0;
+    for (int64_t b = 0; b < p.B; ++b) {
+      op[b] = (int32_t)n;
+      for (int64_t k = 0; k < nc[b]; ++k) ip[n++] = b * p.max_k + k;
+    }
+    op[p.B] = (int32_t)n;
+  }
+  auto flat = hashes.view({-1}).index_select(0, idx_h.to(dev));
+  auto fm = gpu_lookup(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
+                       pods_per_key, flat, model_id, filter_words, num_pods,
+                       epoch, 0, 1, n_tiers);
+  return gpu_score_from_masks(fm[1].contiguous(), off_h.to(dev), weights,
+                              num_pods);
 }
 
 void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,

@@ -74,6 +74,11 @@ std::vector<at::Tensor> gpu_lookup(at::Tensor, at::Tensor, at::Tensor,
                                    at::Tensor, int64_t, int64_t, int64_t,
                                    int64_t, int64_t);
 at::Tensor gpu_score_from_masks(at::Tensor, at::Tensor, at::Tensor, int64_t);
+at::Tensor gpu_score_flat_tokens(at::Tensor, at::Tensor, at::Tensor,
+                                 at::Tensor, at::Tensor, at::Tensor,
+                                 at::Tensor, int64_t, at::Tensor, at::Tensor,
+                                 int64_t, at::Tensor, at::Tensor, int64_t,
+                                 int64_t, int64_t, int64_t, int64_t, int64_t);
 #endif
 
 namespace wire {
@@ -1071,8 +1076,9 @@ class WireFront {
   PromptCache prompt_cache_{2048};
 };
 
-// One-call scoring path for wire batches: parallel CPU chain -> fused
-// probe/score (GPU or CPU table) -> CPU scores.  Registered with the
+// One-call scoring path for wire batches: parallel CPU chain (or, with
+// device_chain, the staged chain on the GPU) -> fused probe/score (GPU
+// or CPU table) -> CPU scores.  Registered with the
 // GIL RELEASED so a second batcher thread can overlap its own batch's
 // parse/launch with this one's kernel sync - and so io threads' Python
 // never stalls behind scoring.
@@ -1084,8 +1090,21 @@ at::Tensor wire_score_flat(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
                            at::Tensor filter_words, at::Tensor weights,
                            int64_t num_pods, int64_t epoch,
                            int64_t init_hash_bits, int64_t block_size,
-                           int64_t n_tiers, int64_t algo) {
+                           int64_t n_tiers, int64_t algo,
+                           int64_t device_chain) {
   int64_t B = offsets.numel() - 1;
+#ifdef KVIDX_WITH_HIP
+  // device_chain=1 (the caller's routing decision, indexer.py
+  // plan_read_route): raw tokens go up and the chain runs on the GPU too.
+  if (device_chain && keys.is_cuda())
+    return gpu_score_flat_tokens(keys, meta, stamp, pods, e_keys, e_meta,
+                                 e_vals, pods_per_key, tokens_flat, offsets,
+                                 model_id, filter_words, weights, num_pods,
+                                 epoch, init_hash_bits, block_size, n_tiers,
+                                 algo)
+        .to(at::kCPU, /*non_blocking=*/false)
+        .contiguous();
+#endif
   auto parents = at::full({B}, init_hash_bits, at::kLong);
   auto chained =
       hash_chain_batch(tokens_flat, offsets, parents, block_size, algo);
@@ -1139,6 +1158,7 @@ void register_wirefront(py::module_& m) {
         py::arg("model_id"), py::arg("filter_words"), py::arg("weights"),
         py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
         py::arg("block_size"), py::arg("n_tiers"), py::arg("algo") = 0,
+        py::arg("device_chain") = 0,
         py::call_guard<py::gil_scoped_release>());
   py::class_<WireFront, std::shared_ptr<WireFront>>(m, "WireFront")
       .def(py::init<py::object, py::object, int64_t, int64_t>(),

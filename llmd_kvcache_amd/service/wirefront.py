@@ -4,7 +4,8 @@ The wirefront (ops/csrc/wirefront.cpp) owns the sockets: epoll io
 threads parse HTTP/1.1 + JSON natively and a batcher thread crosses
 into Python exactly once per micro-batch through the two callbacks
 below.  Python's role per batch is the already-hot scoring path:
-parallel C++ chain (hash_chain_batch) + one fused probe/score kernel.
+parallel C++ chain (hash_chain_batch) + one fused probe/score kernel,
+or the chain on the GPU as well where the indexer's read route says so.
 
     svc = WireIndexerService(indexer)
     port = svc.start(port=8080, n_io=4)
@@ -26,7 +27,7 @@ from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
-from ..indexer import Indexer
+from ..indexer import Indexer, plan_read_route
 from ..utils import hashing
 
 
@@ -100,6 +101,14 @@ class WireIndexerService:
         return (idx, model_id, filt, weights, num_pods, n_tiers,
                 _to_i64(tp.config.init_hash()), tp.block_size)
 
+    def _device_chain(self, idx, offsets, bs) -> int:
+        """The per-batch routing decision (indexer.plan_read_route) as
+        wire_score_flat's trailing argument."""
+        tp = self.indexer.tokens_processor
+        route = plan_read_route(offsets, bs, tp.config.hash_algo,
+                                idx.table.is_cuda, self.indexer.config)
+        return 1 if route.device else 0
+
     @staticmethod
     def _run_flat(idx, *args):
         if idx.table.is_cuda:
@@ -117,7 +126,7 @@ class WireIndexerService:
         scores = self._run_flat(
             idx, *idx.table._t(), tokens_flat, offsets, model_id, filt,
             weights, num_pods, idx.table.next_epoch(), init, bs, n_tiers,
-            self._algo_id)
+            self._algo_id, self._device_chain(idx, offsets, bs))
         return scores, list(idx.registry.id_to_pod)
 
     def _score_text_cb(self, model: str, pods: Sequence[str],
@@ -145,7 +154,7 @@ class WireIndexerService:
         scores = self._run_flat(
             idx, *idx.table._t(), flat_t, off_t, model_id, filt, weights,
             num_pods, idx.table.next_epoch(), init, bs, n_tiers,
-            self._algo_id)
+            self._algo_id, self._device_chain(idx, off_t, bs))
         # 4-tuple: the C++ side feeds elements 2/3 (int32 tokens +
         # offsets) into its prompt cache so repeats skip Python
         return (scores, list(idx.registry.id_to_pod),
