@@ -2,111 +2,11 @@
 // built with KVIDX_WITH_HIP (the default on this ROCm image; hipcc
 // cross-compiles gfx950 without a GPU present).
 
-#include <torch/extension.h>
+#include "kvidx_ops.h"
 
-namespace kvidx {
-
-// cpu_ops.cpp
-std::vector<uint64_t> tokens_to_chunk_hashes(std::vector<uint64_t> tokens,
-                                             uint64_t parent,
-                                             int64_t block_size,
-                                             int64_t algo);
-std::vector<at::Tensor> hash_chain_batch(at::Tensor, at::Tensor, at::Tensor,
-                                         int64_t, int64_t);
-std::vector<uint64_t> tokens_to_chunk_hashes_fast(std::vector<uint64_t>,
-                                                  uint64_t, int64_t, int64_t);
-void cpu_insert(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                at::Tensor, at::Tensor, int64_t, at::Tensor, at::Tensor,
-                int64_t, at::Tensor, int64_t, int64_t, int64_t, int64_t);
-at::Tensor cpu_score_from_masks(at::Tensor, at::Tensor, at::Tensor, int64_t);
-void cpu_compact(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                 at::Tensor, at::Tensor, int64_t, at::Tensor, at::Tensor,
-                 at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor);
-void cpu_evict(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-               at::Tensor, at::Tensor, int64_t, at::Tensor, int64_t,
-               at::Tensor);
-std::vector<at::Tensor> cpu_lookup(at::Tensor, at::Tensor, at::Tensor,
-                                   at::Tensor, at::Tensor, at::Tensor,
-                                   at::Tensor, int64_t, at::Tensor, int64_t,
-                                   at::Tensor, int64_t, int64_t, int64_t,
-                                   int64_t, int64_t);
-at::Tensor cpu_fused_score(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                           at::Tensor, at::Tensor, at::Tensor, int64_t,
-                           at::Tensor, at::Tensor, int64_t, at::Tensor,
-                           at::Tensor, int64_t, int64_t);
-std::vector<at::Tensor> cpu_get_request_keys(at::Tensor, at::Tensor,
-                                             at::Tensor, at::Tensor,
-                                             at::Tensor, at::Tensor,
-                                             at::Tensor, int64_t, at::Tensor,
-                                             int64_t);
-
-#ifdef KVIDX_WITH_HIP
-// hip_ops.hip
-void gpu_insert(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                at::Tensor, at::Tensor, int64_t, at::Tensor, at::Tensor,
-                int64_t, at::Tensor, int64_t, int64_t, int64_t, int64_t);
-void gpu_compact(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                 at::Tensor, at::Tensor, int64_t, at::Tensor, at::Tensor,
-                 at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor);
-void gpu_evict(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-               at::Tensor, at::Tensor, int64_t, at::Tensor, int64_t,
-               at::Tensor);
-std::vector<at::Tensor> gpu_get_request_keys(at::Tensor, at::Tensor,
-                                             at::Tensor, at::Tensor,
-                                             at::Tensor, at::Tensor,
-                                             at::Tensor, int64_t, at::Tensor,
-                                             int64_t);
-std::vector<at::Tensor> gpu_lookup(at::Tensor, at::Tensor, at::Tensor,
-                                   at::Tensor, at::Tensor, at::Tensor,
-                                   at::Tensor, int64_t, at::Tensor, int64_t,
-                                   at::Tensor, int64_t, int64_t, int64_t,
-                                   int64_t, int64_t);
-at::Tensor gpu_fused_score(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                           at::Tensor, at::Tensor, at::Tensor, int64_t,
-                           at::Tensor, at::Tensor, int64_t, at::Tensor,
-                           at::Tensor, int64_t, int64_t, int64_t, int64_t);
-at::Tensor gpu_score_from_masks(at::Tensor, at::Tensor, at::Tensor, int64_t);
-std::vector<at::Tensor> gpu_hash_chain(at::Tensor, at::Tensor, at::Tensor,
-                                       int64_t, int64_t);
-at::Tensor gpu_hash_chain_tr(at::Tensor, at::Tensor, at::Tensor, int64_t,
-                             int64_t, int64_t, int64_t, int64_t);
-at::Tensor gpu_fused_score_rows(at::Tensor, at::Tensor, at::Tensor,
-                                at::Tensor, at::Tensor, at::Tensor,
-                                at::Tensor, int64_t, at::Tensor, at::Tensor,
-                                int64_t, at::Tensor, at::Tensor, int64_t,
-                                int64_t, int64_t, int64_t);
-std::vector<at::Tensor> gpu_stage_ragged_tokens(at::Tensor, at::Tensor,
-                                                int64_t);
-at::Tensor gpu_score_flat_tokens(at::Tensor, at::Tensor, at::Tensor,
-                                 at::Tensor, at::Tensor, at::Tensor,
-                                 at::Tensor, int64_t, at::Tensor, at::Tensor,
-                                 int64_t, at::Tensor, at::Tensor, int64_t,
-                                 int64_t, int64_t, int64_t, int64_t, int64_t);
-void gpu_apply_events(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, at::Tensor, at::Tensor, int64_t, at::Tensor,
-                      at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, int64_t, int64_t, int64_t, int64_t,
-                      int64_t, int64_t);
-void gpu_apply_events_split(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, at::Tensor, int64_t,
-                            at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, at::Tensor, int64_t,
-                            int64_t, int64_t, int64_t, int64_t, int64_t);
-void gpu_apply_events_split_tr(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, at::Tensor, int64_t,
-                            at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, int64_t, int64_t,
-                            int64_t, int64_t, int64_t, int64_t, int64_t);
-#endif
-
-namespace wire {
+namespace kvidx::wire {
 void register_wirefront(pybind11::module_& m);  // wirefront.cpp
 }
-
-}  // namespace kvidx
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native KV-block index ops (CPU reference + gfx950 HIP)";

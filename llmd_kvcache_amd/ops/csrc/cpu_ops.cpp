@@ -7,72 +7,23 @@
 // Thread-safety is provided by the Python-side caller (one writer at a
 // time); the GPU path uses atomics instead (hip_ops.hip).
 
-#include <torch/extension.h>
-
 #include <cstring>
-#include <type_traits>
-#include <vector>
 
-#include "kvidx_common.h"
+#include "kvidx_ops.h"
 
 namespace kvidx {
 
-struct TableView {
-  uint64_t* keys;
-  uint32_t* meta;
-  int32_t* stamp;
-  uint32_t* pods;
-  uint64_t* e_keys;
-  uint32_t* e_meta;
-  uint64_t* e_vals;
-  uint64_t cap_mask;
-  int64_t capacity;
-  int pods_per_key;
-};
-
-static TableView make_view(at::Tensor& keys, at::Tensor& meta,
-                           at::Tensor& stamp, at::Tensor& pods,
-                           at::Tensor& e_keys, at::Tensor& e_meta,
-                           at::Tensor& e_vals, int pods_per_key) {
-  TORCH_CHECK(keys.is_contiguous() && meta.is_contiguous() &&
-                  pods.is_contiguous(),
-              "table tensors must be contiguous");
-  int64_t cap = keys.numel();
-  TORCH_CHECK((cap & (cap - 1)) == 0, "capacity must be a power of two");
-  TableView v;
-  v.keys = reinterpret_cast<uint64_t*>(keys.data_ptr<int64_t>());
-  v.meta = reinterpret_cast<uint32_t*>(meta.data_ptr<int32_t>());
-  v.stamp = stamp.data_ptr<int32_t>();
-  v.pods = reinterpret_cast<uint32_t*>(pods.data_ptr<int32_t>());
-  v.e_keys = reinterpret_cast<uint64_t*>(e_keys.data_ptr<int64_t>());
-  v.e_meta = reinterpret_cast<uint32_t*>(e_meta.data_ptr<int32_t>());
-  v.e_vals = reinterpret_cast<uint64_t*>(e_vals.data_ptr<int64_t>());
-  v.cap_mask = (uint64_t)cap - 1;
-  v.capacity = cap;
-  v.pods_per_key = pods_per_key;
-  return v;
+static int64_t table_find(const Table& v, uint64_t h, uint32_t model) {
+  return probe_find(v.keys, v.meta, v.cap_mask, h, model);
 }
-
-// Probe for an existing live key. Returns slot or -1.
-static int64_t table_find(const TableView& v, uint64_t h, uint32_t model) {
-  h = remap_hash(h);
-  uint64_t s = probe_start(h, v.cap_mask);
-  for (int t = 0; t < PROBE_MAX; ++t) {
-    uint64_t i = (s + t) & v.cap_mask;
-    uint64_t k = v.keys[i];
-    if (k == 0) return -1;  // never-used: chain ends
-    uint32_t m = v.meta[i];
-    if ((m & META_OCC) && !(m & META_TOMB) && k == h &&
-        (m & META_MODEL_MASK) == model)
-      return (int64_t)i;
-  }
-  return -1;
+static int64_t emap_find(const Table& v, uint64_t h, uint32_t model) {
+  return probe_find(v.e_keys, v.e_meta, v.cap_mask, h, model);
 }
 
 // Probe-or-insert. Window-full policy: reuse first tombstone, else
 // overwrite the lowest-stamp live slot (approximate LRU eviction, the
 // CPU analog of the reference's LRU-under-pressure, in_memory.go:32-35).
-static int64_t table_put(const TableView& v, uint64_t h, uint32_t model,
+static int64_t table_put(const Table& v, uint64_t h, uint32_t model,
                          int32_t epoch) {
   h = remap_hash(h);
   uint64_t s = probe_start(h, v.cap_mask);
@@ -115,7 +66,7 @@ static int64_t table_put(const TableView& v, uint64_t h, uint32_t model,
   return i;
 }
 
-static void pod_set_add(const TableView& v, int64_t slot, uint32_t entry,
+static void pod_set_add(const Table& v, int64_t slot, uint32_t entry,
                         int32_t epoch) {
   uint32_t* p = v.pods + slot * v.pods_per_key;
   for (int j = 0; j < v.pods_per_key; ++j)
@@ -130,7 +81,7 @@ static void pod_set_add(const TableView& v, int64_t slot, uint32_t entry,
 
 // ---- engine map (same probing, value payload) ------------------------
 
-static int64_t emap_put(const TableView& v, uint64_t h, uint32_t model,
+static int64_t emap_put(const Table& v, uint64_t h, uint32_t model,
                         uint64_t val, int32_t epoch) {
   h = remap_hash(h);
   uint64_t s = probe_start(h, v.cap_mask);
@@ -168,43 +119,15 @@ static int64_t emap_put(const TableView& v, uint64_t h, uint32_t model,
   return i;
 }
 
-static int64_t emap_find(const TableView& v, uint64_t h, uint32_t model) {
-  h = remap_hash(h);
-  uint64_t s = probe_start(h, v.cap_mask);
-  for (int t = 0; t < PROBE_MAX; ++t) {
-    uint64_t i = (s + t) & v.cap_mask;
-    uint64_t k = v.e_keys[i];
-    if (k == 0) return -1;
-    uint32_t m = v.e_meta[i];
-    if ((m & META_OCC) && !(m & META_TOMB) && k == h &&
-        (m & META_MODEL_MASK) == model)
-      return (int64_t)i;
-  }
-  return -1;
-}
+}  // namespace kvidx
 
 // ---- public ops ------------------------------------------------------
+// Definitions of what kvidx_ops.h declares.  The names are qualified, so
+// a signature that drifts from its declaration does not compile.
 
-// Chain function by native algo id (kvidx_common.h): 0 fnv-64a,
-// 1 sha256-cbor-64, 2 sha256-cbor-64-low.  The id is resolved once per
-// call, outside the chunk loops.
-template <typename F>
-static auto dispatch_algo(int64_t algo, F&& f) {
-  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
-  switch (algo) {
-    case ALGO_SHA256_HI:
-      return f(std::integral_constant<int, ALGO_SHA256_HI>{});
-    case ALGO_SHA256_LOW:
-      return f(std::integral_constant<int, ALGO_SHA256_LOW>{});
-    default:
-      return f(std::integral_constant<int, ALGO_FNV64A>{});
-  }
-}
-
-std::vector<uint64_t> tokens_to_chunk_hashes(std::vector<uint64_t> tokens,
-                                             uint64_t parent,
-                                             int64_t block_size,
-                                             int64_t algo) {
+std::vector<uint64_t> kvidx::tokens_to_chunk_hashes(
+    std::vector<uint64_t> tokens, uint64_t parent, int64_t block_size,
+    int64_t algo) {
   TORCH_CHECK(block_size > 0 && block_size <= 256,
               "block_size must be in (0, 256]");
   std::vector<uint32_t> toks(tokens.begin(), tokens.end());
@@ -229,9 +152,9 @@ std::vector<uint64_t> tokens_to_chunk_hashes(std::vector<uint64_t> tokens,
 // Twin of tokens_to_chunk_hashes over the code the GPU hot path runs, so
 // tests can verify it on every CBOR / SHA padding boundary without a
 // GPU: chunk_hash_fast (branchless FNV) for algo 0, and the
-// encode-whole-payload-then-compress shape of k_hash_chain_tr
+// encode-whole-payload-then-compress shape of k_sha_chain_tr
 // (chunk_hash_sha256_wave) for the SHA algos.
-std::vector<uint64_t> tokens_to_chunk_hashes_fast(
+std::vector<uint64_t> kvidx::tokens_to_chunk_hashes_fast(
     std::vector<uint64_t> tokens, uint64_t parent, int64_t block_size,
     int64_t algo) {
   TORCH_CHECK(block_size > 0, "block_size must be positive");
@@ -264,9 +187,9 @@ std::vector<uint64_t> tokens_to_chunk_hashes_fast(
 // Batched chain hashing: tokens (int64 [total]), offsets (int64 [B+1]),
 // parents (int64 [B], u64 bits) -> per-prompt chunk hashes, flat, with
 // chunk-count offsets returned alongside.
-std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
-                                         at::Tensor parents,
-                                         int64_t block_size, int64_t algo) {
+std::vector<at::Tensor> kvidx::hash_chain_batch(
+    at::Tensor tokens, at::Tensor offsets, at::Tensor parents,
+    int64_t block_size, int64_t algo) {
   TORCH_CHECK(tokens.dtype() == at::kLong && offsets.dtype() == at::kLong &&
               parents.dtype() == at::kLong);
   TORCH_CHECK(block_size > 0, "block_size must be positive");
@@ -276,14 +199,14 @@ std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
   int64_t B = par.numel();
   const int64_t* offp = off.data_ptr<int64_t>();
   const int64_t* tokp = tok.data_ptr<int64_t>();
-  const uint64_t* parp = reinterpret_cast<uint64_t*>(par.data_ptr<int64_t>());
+  const uint64_t* parp = u64p(par);
 
   auto chunk_off = at::zeros({B + 1}, tokens.options());
   int64_t* cop = chunk_off.data_ptr<int64_t>();
   for (int64_t b = 0; b < B; ++b)
     cop[b + 1] = cop[b] + (offp[b + 1] - offp[b]) / block_size;
   auto out = at::empty({cop[B]}, tokens.options());
-  uint64_t* outp = reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>());
+  uint64_t* outp = u64p(out);
 
   dispatch_algo(algo, [&](auto A) {
     at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
@@ -312,16 +235,13 @@ std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
 // into the freshly-zeroed `nw` bundle (optionally a different power-of-
 // two capacity). Stamps (approximate-LRU epochs) and pod rows are
 // carried over verbatim; tombstones and dead probe windows disappear.
-void cpu_compact(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                 at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-                 at::Tensor e_vals, int64_t pods_per_key,
-                 at::Tensor n_keys, at::Tensor n_meta, at::Tensor n_stamp,
-                 at::Tensor n_pods, at::Tensor n_e_keys, at::Tensor n_e_meta,
-                 at::Tensor n_e_vals) {
-  auto ov = make_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                      (int)pods_per_key);
-  auto nv = make_view(n_keys, n_meta, n_stamp, n_pods, n_e_keys, n_e_meta,
-                      n_e_vals, (int)pods_per_key);
+void kvidx::cpu_compact(KVIDX_TABLE_PARAMS, at::Tensor n_keys,
+                        at::Tensor n_meta, at::Tensor n_stamp,
+                        at::Tensor n_pods, at::Tensor n_e_keys,
+                        at::Tensor n_e_meta, at::Tensor n_e_vals) {
+  auto ov = make_table_view(KVIDX_TABLE_ARGS, false);
+  auto nv = make_table_view(n_keys, n_meta, n_stamp, n_pods, n_e_keys,
+                            n_e_meta, n_e_vals, pods_per_key, false);
   int64_t cap = keys.numel();
   for (int64_t i = 0; i < cap; ++i) {
     uint32_t m = ov.meta[i];
@@ -344,20 +264,17 @@ void cpu_compact(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
 // (request_hash % num_shards == shard_id); the engine->request map is
 // replicated on every shard so parent-chain stitching never needs a
 // cross-rank lookup (see parallel/sharded.py).
-void cpu_insert(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-                at::Tensor e_vals, int64_t pods_per_key,
-                at::Tensor engine_hashes, at::Tensor request_hashes,
-                int64_t model_id, at::Tensor pod_entries, int64_t epoch,
-                int64_t shard_id, int64_t num_shards, int64_t emap_write) {
-  auto v = make_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                     (int)pods_per_key);
+void kvidx::cpu_insert(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
+                       at::Tensor request_hashes, int64_t model_id,
+                       at::Tensor pod_entries, int64_t epoch, int64_t shard_id,
+                       int64_t num_shards, int64_t emap_write) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
   auto eh = engine_hashes.contiguous();
   auto rh = request_hashes.contiguous();
   auto pe = pod_entries.contiguous();
-  const uint64_t* ehp = reinterpret_cast<uint64_t*>(eh.data_ptr<int64_t>());
-  const uint64_t* rhp = reinterpret_cast<uint64_t*>(rh.data_ptr<int64_t>());
-  const uint32_t* pep = reinterpret_cast<uint32_t*>(pe.data_ptr<int32_t>());
+  const uint64_t* ehp = u64p(eh);
+  const uint64_t* rhp = u64p(rh);
+  const uint32_t* pep = u32p(pe);
   int64_t n = eh.numel();
   int64_t m = pe.numel();
   TORCH_CHECK(rh.numel() == n, "engine/request key length mismatch");
@@ -365,9 +282,7 @@ void cpu_insert(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
     if (emap_write)
       emap_put(v, ehp[i], (uint32_t)model_id, remap_hash(rhp[i]),
                (int32_t)epoch);
-    if (num_shards > 1 &&
-        (int64_t)(remap_hash(rhp[i]) % (uint64_t)num_shards) != shard_id)
-      continue;
+    if (!owns_key(rhp[i], (int)shard_id, (int)num_shards)) continue;
     int64_t slot = table_put(v, rhp[i], (uint32_t)model_id, (int32_t)epoch);
     for (int64_t j = 0; j < m; ++j)
       pod_set_add(v, slot, pep[j], (int32_t)epoch);
@@ -376,17 +291,17 @@ void cpu_insert(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
 
 // Walk precomputed (possibly all-reduce-merged) masks -> scores; CPU twin
 // of k_score_from_masks for gloo-backed multi-process tests.
-at::Tensor cpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
-                                at::Tensor weights, int64_t num_pods) {
+at::Tensor kvidx::cpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
+                                       at::Tensor weights, int64_t num_pods) {
   auto m = masks.contiguous();
   auto off = offsets.contiguous();
   TORCH_CHECK(m.dim() == 3, "masks must be [Ktot, T, W]");
   const int64_t T = m.size(1);  // tier planes (sized by caller)
-  const uint64_t* mp = reinterpret_cast<uint64_t*>(m.data_ptr<int64_t>());
+  const uint64_t* mp = u64p(m);
   const int32_t* op = off.data_ptr<int32_t>();
   const float* wts = weights.data_ptr<float>();
   int64_t B = off.numel() - 1;
-  int64_t W = (num_pods + 63) / 64;
+  int64_t W = pod_words(num_pods);
   TORCH_CHECK(W <= 64, "num_pods > 4096 not supported");
   auto scores = at::zeros({B, num_pods}, at::kFloat);
   float* sp = scores.data_ptr<float>();
@@ -421,17 +336,13 @@ at::Tensor cpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
   return scores;
 }
 
-void cpu_evict(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-               at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-               at::Tensor e_vals, int64_t pods_per_key,
-               at::Tensor engine_hashes, int64_t model_id,
-               at::Tensor pod_entries) {
-  auto v = make_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                     (int)pods_per_key);
+void kvidx::cpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
+                      int64_t model_id, at::Tensor pod_entries) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
   auto eh = engine_hashes.contiguous();
   auto pe = pod_entries.contiguous();
-  const uint64_t* ehp = reinterpret_cast<uint64_t*>(eh.data_ptr<int64_t>());
-  const uint32_t* pep = reinterpret_cast<uint32_t*>(pe.data_ptr<int32_t>());
+  const uint64_t* ehp = u64p(eh);
+  const uint32_t* pep = u32p(pe);
   // Engine->request mappings are deliberately RETAINED on eviction
   // (unlike in_memory.go:252-255): with the sharded deployment the emap
   // is replicated while the main table is ownership-filtered, so only
@@ -459,39 +370,32 @@ void cpu_evict(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
 
 // found: 0 absent, 1 present-with-visible-pods, 2 present-but-empty
 // (chain-cut marker, in_memory.go:118-121).
-std::vector<at::Tensor> cpu_lookup(at::Tensor keys, at::Tensor meta,
-                                   at::Tensor stamp, at::Tensor pods,
-                                   at::Tensor e_keys, at::Tensor e_meta,
-                                   at::Tensor e_vals, int64_t pods_per_key,
-                                   at::Tensor request_hashes, int64_t model_id,
-                                   at::Tensor filter_words, int64_t num_pods,
-                                   int64_t epoch, int64_t shard_id,
-                                   int64_t num_shards,
-                                   int64_t n_tiers) {
-  auto v = make_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                     (int)pods_per_key);
+std::vector<at::Tensor> kvidx::cpu_lookup(KVIDX_TABLE_PARAMS,
+                                          at::Tensor request_hashes,
+                                          int64_t model_id,
+                                          at::Tensor filter_words,
+                                          int64_t num_pods, int64_t epoch,
+                                          int64_t shard_id, int64_t num_shards,
+                                          int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
   auto rh = request_hashes.contiguous();
-  const uint64_t* rhp = reinterpret_cast<uint64_t*>(rh.data_ptr<int64_t>());
+  const uint64_t* rhp = u64p(rh);
   int64_t K = rh.numel();
-  int64_t W = (num_pods + 63) / 64;
+  int64_t W = pod_words(num_pods);
   bool has_filter = filter_words.numel() > 0;
-  const uint64_t* fw = has_filter ? reinterpret_cast<uint64_t*>(
-                                        filter_words.data_ptr<int64_t>())
-                                  : nullptr;
+  const uint64_t* fw = has_filter ? u64p(filter_words) : nullptr;
 
-  if (n_tiers < 1) n_tiers = 1;
-  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
+  n_tiers = clamp_tiers(n_tiers);
   auto found = at::zeros({K}, at::kByte);
   // masks sized by the REGISTERED tier count (usually 1-2): halves-to-
   // quarters the fallback path's mask traffic and the sharded
   // all_reduce bytes vs a fixed MAX_TIERS=4 plane count.
   auto masks = at::zeros({K, n_tiers, W}, at::kLong);
   uint8_t* fp = found.data_ptr<uint8_t>();
-  uint64_t* mp = reinterpret_cast<uint64_t*>(masks.data_ptr<int64_t>());
+  uint64_t* mp = u64p(masks);
 
   for (int64_t k = 0; k < K; ++k) {
-    if (num_shards > 1 &&
-        (int64_t)(remap_hash(rhp[k]) % (uint64_t)num_shards) != shard_id)
+    if (!owns_key(rhp[k], (int)shard_id, (int)num_shards))
       continue;  // unowned key: another shard's mask contribution
     int64_t slot = table_find(v, rhp[k], (uint32_t)model_id);
     if (slot < 0) continue;
@@ -517,25 +421,19 @@ std::vector<at::Tensor> cpu_lookup(at::Tensor keys, at::Tensor meta,
 
 // Fused probe + longest-prefix score (the read-path hot loop, scoring
 // parity with kvblock_scorer.go:108-151).
-at::Tensor cpu_fused_score(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                           at::Tensor pods, at::Tensor e_keys,
-                           at::Tensor e_meta, at::Tensor e_vals,
-                           int64_t pods_per_key, at::Tensor hashes,
-                           at::Tensor counts, int64_t model_id,
-                           at::Tensor filter_words, at::Tensor weights,
-                           int64_t num_pods, int64_t epoch) {
-  auto v = make_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                     (int)pods_per_key);
+at::Tensor kvidx::cpu_fused_score(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                  at::Tensor counts, int64_t model_id,
+                                  at::Tensor filter_words, at::Tensor weights,
+                                  int64_t num_pods, int64_t epoch) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
   auto h = hashes.contiguous();
   auto cnt = counts.contiguous();
-  const uint64_t* hp = reinterpret_cast<uint64_t*>(h.data_ptr<int64_t>());
+  const uint64_t* hp = u64p(h);
   const int32_t* cp = cnt.data_ptr<int32_t>();
   int64_t B = cnt.numel();
-  int64_t W = (num_pods + 63) / 64;
+  int64_t W = pod_words(num_pods);
   bool has_filter = filter_words.numel() > 0;
-  const uint64_t* fw = has_filter ? reinterpret_cast<uint64_t*>(
-                                        filter_words.data_ptr<int64_t>())
-                                  : nullptr;
+  const uint64_t* fw = has_filter ? u64p(filter_words) : nullptr;
   const float* wts = weights.data_ptr<float>();
 
   TORCH_CHECK(W <= 64, "num_pods > 4096 not supported");
@@ -602,19 +500,16 @@ at::Tensor cpu_fused_score(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
   return scores;
 }
 
-std::vector<at::Tensor> cpu_get_request_keys(
-    at::Tensor keys, at::Tensor meta, at::Tensor stamp, at::Tensor pods,
-    at::Tensor e_keys, at::Tensor e_meta, at::Tensor e_vals,
-    int64_t pods_per_key, at::Tensor engine_hashes, int64_t model_id) {
-  auto v = make_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                     (int)pods_per_key);
+std::vector<at::Tensor> kvidx::cpu_get_request_keys(
+    KVIDX_TABLE_PARAMS, at::Tensor engine_hashes, int64_t model_id) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
   auto eh = engine_hashes.contiguous();
-  const uint64_t* ehp = reinterpret_cast<uint64_t*>(eh.data_ptr<int64_t>());
+  const uint64_t* ehp = u64p(eh);
   int64_t n = eh.numel();
   auto found = at::zeros({n}, at::kByte);
   auto out = at::zeros({n}, at::kLong);
   uint8_t* fp = found.data_ptr<uint8_t>();
-  uint64_t* op = reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>());
+  uint64_t* op = u64p(out);
   for (int64_t i = 0; i < n; ++i) {
     int64_t ei = emap_find(v, ehp[i], (uint32_t)model_id);
     if (ei >= 0) {
@@ -624,5 +519,3 @@ std::vector<at::Tensor> cpu_get_request_keys(
   }
   return {found, out};
 }
-
-}  // namespace kvidx

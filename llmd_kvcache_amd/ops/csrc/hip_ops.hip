@@ -9,60 +9,47 @@
 //    PARALLEL (the prefix early-stop is applied after the fact during the
 //    in-LDS mask walk), so per-prompt latency is ~2 dependent HBM reads,
 //    not K of them - the CPU reference walks keys serially;
-//  - per-(key,tier) pod-bitmask accumulation in LDS, then a single wave
-//    walks the masks in key order computing longest-prefix scores with the
-//    active pod set in registers (lane l owns pod bit l of each 64-pod
-//    word) - scoring parity with kvblock_scorer.go:108-151;
+//  - per-(key,tier) pod-bitmask accumulation in LDS, then the workgroup's
+//    four waves walk the masks in key order, each taking every fourth
+//    64-pod word, computing longest-prefix scores with the active pod set
+//    in registers (lane l owns pod bit l of its word) - scoring parity
+//    with kvblock_scorer.go:108-151;
 //  - write path: events arrive grouped by pod (per-pod ordering guarantee
-//    of kvevents/pool.go:132-144 preserved); one wave per pod-group
-//    processes its events serially; within a BlockStored event lane 0
-//    streams the serial FNV/CBOR chain (token_processor.go:94-123) while
-//    block inserts fan out across all 64 lanes;
-//  - hash-chain batch kernel: one lane per prompt, chain in registers
-//    (streaming CBOR->FNV, no scratch), wave64-dense.
+//    of kvevents/pool.go:132-144 preserved).  The usual route is phase
+//    split: request-key chains one lane per event (or per pod-group when
+//    a batch refers to its own blocks as parents), then one thread per
+//    block for the inserts and removals.  A batch that stores and removes
+//    the same engine hash takes the serial kernel: one wave per
+//    pod-group, lane 0 streams the chain (token_processor.go:94-123)
+//    and the block inserts fan out across the 64 lanes;
+//  - hash-chain batch kernels: one lane per prompt over transposed
+//    tokens, wave64-dense; the FNV chain lives in registers (streaming
+//    CBOR->FNV, no scratch), the SHA-256 chain packs its payload into an
+//    LDS column per lane.
+// Each table decision (probe, remove, store, ownership, parent, event
+// length) is one device helper below; the kernels are calls to them.
 
 #include <hip/hip_runtime.h>
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-#include "kvidx_common.h"
+#include "kvidx_ops.h"
 
 namespace kvidx {
 
 #define DEV __device__ __forceinline__
 
-struct DevTable {
-  uint64_t* __restrict__ keys;
-  uint32_t* __restrict__ meta;
-  int32_t* __restrict__ stamp;
-  uint32_t* __restrict__ pods;
-  uint64_t* __restrict__ e_keys;
-  uint32_t* __restrict__ e_meta;
-  uint64_t* __restrict__ e_vals;
-  uint64_t cap_mask;
-  int pods_per_key;
-};
-
-DEV int64_t dev_table_find(const DevTable& v, uint64_t h, uint32_t model) {
-  h = remap_hash(h);
-  uint64_t s = probe_start(h, v.cap_mask);
-  for (int t = 0; t < PROBE_MAX; ++t) {
-    uint64_t i = (s + t) & v.cap_mask;
-    uint64_t k = v.keys[i];
-    if (k == 0) return -1;
-    uint32_t m = v.meta[i];
-    if ((m & META_OCC) && !(m & META_TOMB) && k == h &&
-        (m & META_MODEL_MASK) == model)
-      return (int64_t)i;
-  }
-  return -1;
+DEV int64_t dev_table_find(const Table& v, uint64_t h, uint32_t model) {
+  return probe_find(v.keys, v.meta, v.cap_mask, h, model);
+}
+DEV int64_t dev_emap_find(const Table& v, uint64_t h, uint32_t model) {
+  return probe_find(v.e_keys, v.e_meta, v.cap_mask, h, model);
 }
 
 // Lock-free probe-or-insert. Claims free slots via atomicCAS on the key
 // word (deterministic probe order makes same-key racers converge on the
 // same slot); tombstone resurrection via atomicCAS on meta; window-full
 // falls back to stealing the lowest-stamp live slot (approx LRU).
-DEV int64_t dev_table_put(const DevTable& v, uint64_t h, uint32_t model,
+DEV int64_t dev_table_put(const Table& v, uint64_t h, uint32_t model,
                           int32_t epoch) {
   h = remap_hash(h);
   uint64_t s = probe_start(h, v.cap_mask);
@@ -121,7 +108,7 @@ DEV int64_t dev_table_put(const DevTable& v, uint64_t h, uint32_t model,
   return i;
 }
 
-DEV void dev_pod_set_add(const DevTable& v, int64_t slot, uint32_t entry,
+DEV void dev_pod_set_add(const Table& v, int64_t slot, uint32_t entry,
                          int32_t epoch) {
   KVIDX_ASSERT(slot >= 0 && (uint64_t)slot <= v.cap_mask);
   KVIDX_ASSERT(entry != 0);
@@ -140,7 +127,7 @@ DEV void dev_pod_set_add(const DevTable& v, int64_t slot, uint32_t entry,
   atomicExch(&p[(uint32_t)epoch % v.pods_per_key], entry);  // full: overwrite
 }
 
-DEV void dev_emap_put(const DevTable& v, uint64_t h, uint32_t model,
+DEV void dev_emap_put(const Table& v, uint64_t h, uint32_t model,
                       uint64_t val) {
   h = remap_hash(h);
   uint64_t s = probe_start(h, v.cap_mask);
@@ -186,27 +173,72 @@ DEV void dev_emap_put(const DevTable& v, uint64_t h, uint32_t model,
   atomicExch(&v.e_meta[i], META_OCC | (model & META_MODEL_MASK));
 }
 
-DEV int64_t dev_emap_find(const DevTable& v, uint64_t h, uint32_t model) {
-  h = remap_hash(h);
-  uint64_t s = probe_start(h, v.cap_mask);
-  for (int t = 0; t < PROBE_MAX; ++t) {
-    uint64_t i = (s + t) & v.cap_mask;
-    uint64_t k = v.e_keys[i];
-    if (k == 0) return -1;
-    uint32_t m = v.e_meta[i];
-    if ((m & META_OCC) && !(m & META_TOMB) && k == h &&
-        (m & META_MODEL_MASK) == model)
-      return (int64_t)i;
-  }
-  return -1;
+// Remove the n pod entries from the block an engine hash maps to and
+// tombstone the block when its pod set empties.  The engine mapping is
+// retained (replica determinism under sharding + chain continuity; see
+// the cpu_evict note).  Entries outer, slots inner.
+DEV void dev_remove_pods(const Table& v, uint64_t engine_hash, uint32_t model,
+                         const uint32_t* __restrict__ entries, int n) {
+  int64_t ei = dev_emap_find(v, engine_hash, model);
+  if (ei < 0) return;
+  uint64_t req = v.e_vals[ei];
+  int64_t slot = dev_table_find(v, req, model);
+  if (slot < 0) return;
+  uint32_t* p = v.pods + slot * v.pods_per_key;
+  for (int j = 0; j < n; ++j)
+    for (int k = 0; k < v.pods_per_key; ++k)
+      atomicCAS(&p[k], entries[j], 0u);
+  bool empty = true;
+  for (int k = 0; k < v.pods_per_key; ++k)
+    if (p[k] != 0) { empty = false; break; }
+  if (empty) atomicOr(&v.meta[slot], META_TOMB);
 }
 
-// Probe one key and OR its visible pod entries into per-tier mask words.
+// Store one block: publish engine hash -> request key (on every shard: the
+// engine map is replicated), then, on the shard that owns the request
+// key, insert it and add the n pod entries.
+DEV void dev_store_block(const Table& v, uint64_t engine_hash, uint64_t req,
+                         uint32_t model, const uint32_t* __restrict__ entries,
+                         int n, int32_t epoch, int shard_id, int num_shards,
+                         int emap_write) {
+  if (emap_write) dev_emap_put(v, engine_hash, model, remap_hash(req));
+  if (!owns_key(req, shard_id, num_shards)) return;
+  int64_t slot = dev_table_put(v, req, model, epoch);
+  for (int j = 0; j < n; ++j) dev_pod_set_add(v, slot, entries[j], epoch);
+}
+
+// Chunk count of BlockStored event e, or -1 when its engine-hash count
+// differs from the token-derived chain length.  The reference Add() (and
+// the CPU digest path) rejects such an event whole; every kernel that
+// reads an event asks here, so CPU and GPU replicas stay convergent on
+// malformed streams.
+DEV int event_chain_len(const int32_t* __restrict__ tok_off,
+                        const int32_t* __restrict__ eh_off, int64_t e,
+                        int block_size) {
+  KVIDX_ASSERT(eh_off[e + 1] >= eh_off[e] && tok_off[e + 1] >= tok_off[e]);
+  const int n_chunks = (tok_off[e + 1] - tok_off[e]) / block_size;
+  return n_chunks == eh_off[e + 1] - eh_off[e] ? n_chunks : -1;
+}
+
+// Chain parent of event e: the request key its parent engine hash maps to
+// in the persistent engine map, else (no parent, or unknown) the root.
+DEV uint64_t dev_event_parent(const Table& v,
+                              const uint8_t* __restrict__ has_parent,
+                              const uint64_t* __restrict__ parents,
+                              const int32_t* __restrict__ model_of, int64_t e,
+                              uint64_t init_hash) {
+  if (!has_parent[e]) return init_hash;
+  int64_t ei = dev_emap_find(v, parents[e], (uint32_t)model_of[e]);
+  return ei >= 0 ? v.e_vals[ei] : init_hash;
+}
+
+// Probe one key and OR its visible pod entries into its per-tier mask
+// words mk [n_tiers, W] (LDS or global).
 // Returns: 0 absent, 1 present (raw pods nonzero), 2 present-but-empty.
-template <typename OrFn>
-DEV int dev_probe_collect(const DevTable& v, uint64_t h, uint32_t model,
+DEV int dev_probe_collect(const Table& v, uint64_t h, uint32_t model,
                           const uint64_t* __restrict__ filter, int has_filter,
-                          int num_pods, int W, int32_t epoch, OrFn&& or_bit) {
+                          int num_pods, int W, int32_t epoch,
+                          unsigned long long* mk, int n_tiers) {
   int64_t slot = dev_table_find(v, h, model);
   if (slot < 0) return 0;
   v.stamp[slot] = epoch;  // LRU touch on read (non-atomic ok)
@@ -220,7 +252,8 @@ DEV int dev_probe_collect(const DevTable& v, uint64_t h, uint32_t model,
     uint32_t tier = pod_entry_tier(e);
     if (pid >= (uint32_t)num_pods || tier >= MAX_TIERS) continue;
     if (has_filter && !((filter[pid / 64] >> (pid % 64)) & 1)) continue;
-    or_bit(tier, pid);
+    if ((int)tier < n_tiers)  // interned => always true
+      atomicOr(&mk[tier * W + pid / 64], 1ull << (pid % 64));
   }
   return any_raw ? 1 : 2;
 }
@@ -229,26 +262,21 @@ DEV int dev_probe_collect(const DevTable& v, uint64_t h, uint32_t model,
 // Kernels
 // ---------------------------------------------------------------------
 
-__global__ void k_insert(DevTable v, const uint64_t* __restrict__ eh,
+__global__ void k_insert(Table v, const uint64_t* __restrict__ eh,
                          const uint64_t* __restrict__ rh, int64_t n,
                          uint32_t model, const uint32_t* __restrict__ entries,
                          int n_entries, int32_t epoch, int shard_id,
                          int num_shards, int emap_write) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (emap_write) dev_emap_put(v, eh[i], model, remap_hash(rh[i]));
-  if (num_shards > 1 &&
-      (int)(remap_hash(rh[i]) % (uint64_t)num_shards) != shard_id)
-    return;  // engine map replicated; main table sharded by ownership
-  int64_t slot = dev_table_put(v, rh[i], model, epoch);
-  for (int j = 0; j < n_entries; ++j)
-    dev_pod_set_add(v, slot, entries[j], epoch);
+  dev_store_block(v, eh[i], rh[i], model, entries, n_entries, epoch, shard_id,
+                  num_shards, emap_write);
 }
 
 // Tombstone compaction (ROADMAP #9): thread per OLD slot rehashes live
 // entries into a fresh bundle (lock-free via the usual CAS claims; old
 // (key,model) pairs are unique so racers only contend on free slots).
-__global__ void k_compact_main(DevTable ov, DevTable nv, int64_t cap) {
+__global__ void k_compact_main(Table ov, Table nv, int64_t cap) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cap) return;
   uint32_t m = ov.meta[i];
@@ -260,7 +288,7 @@ __global__ void k_compact_main(DevTable ov, DevTable nv, int64_t cap) {
   for (int j = 0; j < nv.pods_per_key; ++j) dst[j] = src[j];
 }
 
-__global__ void k_compact_emap(DevTable ov, DevTable nv, int64_t cap) {
+__global__ void k_compact_emap(Table ov, Table nv, int64_t cap) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cap) return;
   uint32_t m = ov.e_meta[i];
@@ -268,29 +296,15 @@ __global__ void k_compact_emap(DevTable ov, DevTable nv, int64_t cap) {
   dev_emap_put(nv, ov.e_keys[i], m & META_MODEL_MASK, ov.e_vals[i]);
 }
 
-__global__ void k_evict(DevTable v, const uint64_t* __restrict__ eh,
+__global__ void k_evict(Table v, const uint64_t* __restrict__ eh,
                         int64_t n, uint32_t model,
                         const uint32_t* __restrict__ entries, int n_entries) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // emap entries retained on eviction (replica determinism under
-  // sharding + chain continuity; see cpu_evict note).
-  int64_t ei = dev_emap_find(v, eh[i], model);
-  if (ei < 0) return;
-  uint64_t req = v.e_vals[ei];
-  int64_t slot = dev_table_find(v, req, model);
-  if (slot < 0) return;
-  uint32_t* p = v.pods + slot * v.pods_per_key;
-  for (int j = 0; j < n_entries; ++j)
-    for (int k = 0; k < v.pods_per_key; ++k)
-      atomicCAS(&p[k], entries[j], 0u);
-  bool empty = true;
-  for (int k = 0; k < v.pods_per_key; ++k)
-    if (p[k] != 0) { empty = false; break; }
-  if (empty) atomicOr(&v.meta[slot], META_TOMB);
+  dev_remove_pods(v, eh[i], model, entries, n_entries);
 }
 
-__global__ void k_get_request_keys(DevTable v,
+__global__ void k_get_request_keys(Table v,
                                    const uint64_t* __restrict__ eh, int64_t n,
                                    uint32_t model, uint8_t* __restrict__ found,
                                    uint64_t* __restrict__ out) {
@@ -304,7 +318,7 @@ __global__ void k_get_request_keys(DevTable v,
 }
 
 // Generic lookup producing global found[] + per-tier masks [K, T, W].
-__global__ void k_lookup_masks(DevTable v, const uint64_t* __restrict__ rh,
+__global__ void k_lookup_masks(Table v, const uint64_t* __restrict__ rh,
                                int64_t K, uint32_t model,
                                const uint64_t* __restrict__ filter,
                                int has_filter, int num_pods, int W,
@@ -314,29 +328,44 @@ __global__ void k_lookup_masks(DevTable v, const uint64_t* __restrict__ rh,
                                unsigned long long* __restrict__ masks) {
   int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
-  if (num_shards > 1 &&
-      (int)(remap_hash(rh[k]) % (uint64_t)num_shards) != shard_id)
+  if (!owns_key(rh[k], shard_id, num_shards))
     return;  // unowned key: contributes zero masks on this shard
-  unsigned long long* mk = masks + (size_t)k * n_tiers * W;
-  int f = dev_probe_collect(
+  found[k] = (uint8_t)dev_probe_collect(
       v, rh[k], model, filter, has_filter, num_pods, W, epoch,
-      [&](uint32_t tier, uint32_t pid) {
-        if ((int)tier < n_tiers)  // interned => always true
-          atomicOr(&mk[tier * W + pid / 64], 1ull << (pid % 64));
-      });
-  found[k] = (uint8_t)f;
+      masks + (size_t)k * n_tiers * W, n_tiers);
+}
+
+// One (key, word) step of the longest-prefix walk, lane = pod bit.  mk is
+// the key's tier-0 mask word for this 64-pod word (tier planes W apart).
+// A pod stays active while every key so far lists it; an active pod earns
+// the key's best tier weight.  Returns the lane's new active flag.
+DEV int score_walk_step(const unsigned long long* mk, int W, int n_tiers,
+                        const float* __restrict__ weights, int lane,
+                        bool first, int& active, float& score) {
+  int cur = 0;
+  float wmax = 0.f;
+  for (int t = 0; t < n_tiers; ++t) {
+    if ((mk[t * W] >> lane) & 1) {
+      cur = 1;
+      wmax = fmaxf(wmax, weights[t]);
+    }
+  }
+  int act = first ? cur : (active & cur);
+  active = act;
+  if (act) score += wmax;
+  return act;
 }
 
 // Fused probe + longest-prefix score. One workgroup per prompt; dynamic
-// LDS holds the per-key per-tier masks; wave 0 then walks keys in order
-// with the active pod set in registers (lane l = pod bit l).
+// LDS holds the per-key per-tier masks; the four waves then walk keys in
+// order, a 64-pod word each, with the active pod set in registers.
 //
 // The body is shared by two entries that differ only in where prompt b's
 // keys lie: k_fused_score takes flat hashes with offsets [B+1],
 // k_fused_score_rows takes padded rows (h = hashes + b * stride, K =
 // n_keys[b]) as the row-major chain kernel leaves them.
 DEV void fused_score_body(
-    DevTable v, const uint64_t* __restrict__ h, const int K,
+    Table v, const uint64_t* __restrict__ h, const int K,
     uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
     const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
     int n_tiers, float* __restrict__ scores) {
@@ -354,15 +383,9 @@ DEV void fused_score_body(
   __syncthreads();
 
   // phase 1: all probes in parallel (each is ~2 dependent HBM reads)
-  for (int k = threadIdx.x; k < K; k += blockDim.x) {
-    unsigned long long* mk = lds_masks + (size_t)k * n_tiers * W;
+  for (int k = threadIdx.x; k < K; k += blockDim.x)
     dev_probe_collect(v, h[k], model, filter, has_filter, num_pods, W, epoch,
-                      [&](uint32_t tier, uint32_t pid) {
-                        if ((int)tier < n_tiers)  // interned => always true
-                          atomicOr(&mk[tier * W + pid / 64],
-                                   1ull << (pid % 64));
-                      });
-  }
+                      lds_masks + (size_t)k * n_tiers * W, n_tiers);
   __syncthreads();
 
   // phase 2: the walk. Words (64-pod groups) are independent prefix
@@ -374,19 +397,9 @@ DEV void fused_score_body(
     float score = 0.f;
     int active = 0;
     for (int k = 0; k < K; ++k) {
-      const unsigned long long* mk =
-          lds_masks + (size_t)k * n_tiers * W + w;
-      int cur = 0;
-      float wmax = 0.f;
-      for (int t = 0; t < n_tiers; ++t) {
-        if ((mk[t * W] >> lane) & 1) {
-          cur = 1;
-          wmax = fmaxf(wmax, weights[t]);
-        }
-      }
-      int act = (k == 0) ? cur : (active & cur);
-      active = act;
-      if (act) score += wmax;
+      const int act =
+          score_walk_step(lds_masks + (size_t)k * n_tiers * W + w, W, n_tiers,
+                          weights, lane, k == 0, active, score);
       if (!__any(act)) break;  // this word's active set is empty
     }
     int pid = w * 64 + lane;
@@ -395,7 +408,7 @@ DEV void fused_score_body(
 }
 
 __global__ void __launch_bounds__(256) k_fused_score(
-    DevTable v, const uint64_t* __restrict__ hashes,
+    Table v, const uint64_t* __restrict__ hashes,
     const int32_t* __restrict__ offsets,  // [B+1]
     uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
     const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
@@ -410,7 +423,7 @@ __global__ void __launch_bounds__(256) k_fused_score(
 // slots past n_keys[b] are never read (the chain kernel zeroes them, and
 // remap_hash(0) is a legal key).
 __global__ void __launch_bounds__(256) k_fused_score_rows(
-    DevTable v, const uint64_t* __restrict__ hashes,  // [B, stride]
+    Table v, const uint64_t* __restrict__ hashes,  // [B, stride]
     const int32_t* __restrict__ n_keys,               // [B]
     int64_t stride, uint32_t model, const uint64_t* __restrict__ filter,
     int has_filter, const float* __restrict__ weights, int num_pods, int W,
@@ -447,17 +460,8 @@ __global__ void __launch_bounds__(64) k_score_from_masks(
         masks + (size_t)(offsets[b] + k) * T * W;
     bool any = false;
     for (int w = 0; w < WG; ++w) {
-      int cur = 0;
-      float wmax = 0.f;
-      for (int t = 0; t < T; ++t) {
-        if ((mk[t * W + w_lo + w] >> lane) & 1) {
-          cur = 1;
-          wmax = fmaxf(wmax, weights[t]);
-        }
-      }
-      int act = (k == 0) ? cur : (active[w] & cur);
-      active[w] = act;
-      if (act) score[w] += wmax;
+      const int act = score_walk_step(mk + w_lo + w, W, T, weights, lane,
+                                      k == 0, active[w], score[w]);
       if (__any(act)) any = true;
     }
     if (!any) break;
@@ -499,20 +503,23 @@ __global__ void k_hash_chain(const int64_t* __restrict__ tokens,
 // measured 2.5 ms per 512x512-chunk call on MI355X - pure HBM latency on
 // strided per-lane loads; this layout removes that.
 // out is [max_chunks][B] (transposed too; callers transpose back with a
-// cheap torch op or consume the stride directly).
-// ILP chains: each lane advances ILP independent prompt chains in one
-// straight-line (branchless chunk_hash_fast) loop body.  Measured, this
-// does not pay: with one wave per SIMD the wave is instruction-ISSUE
-// bound (one vector instruction per ~5 cycles, dependent or not), so
-// ILP-x issues x times the instructions in nearly x times the time
-// (profiles/r01_chain_sweep.md, profiles/r04_fnv_chain.md).  What makes
-// a call faster is fewer instructions per chunk; ILP 1 is the default.
-// Lane l of the grid owns prompts {l, l+L, .., l+(ILP-1)L} where
-// L = total lanes, keeping every token load coalesced.
-// The kernel writes EVERY slot of out for its prompts, a zero where
+// cheap torch op or consume the stride directly) or, row_major, [B]
+// [max_chunks] as the fused-score kernel reads it.
+// One chain per lane.  Several chains per lane (ILP) and an explicit
+// double-buffer prefetch were both built and measured slower in every
+// round: with one wave per SIMD the wave is instruction-ISSUE bound (one
+// vector instruction per ~5 cycles, dependent or not), so x chains per
+// lane take nearly x times the time (profiles/r01_chain_sweep.md,
+// r04_fnv_chain.md, r05_score_walk.md, r07_native_refactor.md).  What
+// makes a call faster is fewer instructions per chunk.
+// The kernels write EVERY slot of out for their prompts, a zero where
 // c >= n_chunks[b], so the caller need not clear the buffer first.
-//
-// SHA-256 policy (ALGO 1/2, ILP 1): not a re-skin of the FNV body.  FNV
+DEV int64_t chain_out_index(int row_major, int64_t b, int c, int max_chunks,
+                            int64_t B) {
+  return row_major ? b * max_chunks + c : (int64_t)c * B + b;
+}
+
+// SHA-256 chain (ALGO 1/2): not a re-skin of the FNV body.  FNV
 // streams bytes through one 64-bit register; SHA-256 needs 16-word
 // blocks and CBOR makes every byte position data-dependent per lane.
 // Each lane therefore first packs its whole padded payload (1..6 blocks
@@ -537,8 +544,45 @@ constexpr int sha_tr_words(int bs) {
   return 16 * sha_blocks_for(sha_max_payload(bs));
 }
 
-// Row-major staging of the FNV ILP-1 chain (see the kernel): chunks per
-// flush, u64 per staged prompt row (one pad), dynamic LDS per workgroup.
+template <int BS, int ALGO>
+__global__ void k_sha_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
+                               const uint64_t* __restrict__ parents,  // [B]
+                               const int32_t* __restrict__ n_chunks,  // [B]
+                               int64_t B, int max_chunks, int row_major,
+                               uint64_t* __restrict__ out) {  // [maxC,B] or [B,maxC]
+  constexpr int NT = sha_tr_threads(BS);
+  __shared__ uint32_t sha_words[sha_tr_words(BS) * NT];
+  const int64_t lane = (int64_t)blockIdx.x * NT + threadIdx.x;
+  // no early return: idle lanes ride along (clamped loads, results
+  // discarded) so every wave-wide vote below sees whole waves
+  const bool live = lane < B;
+  const int64_t bi = live ? lane : 0;
+  uint64_t h = parents[bi];
+  const int mc = live ? n_chunks[bi] : 0;
+  ShaLdsCol<NT> col{sha_words + threadIdx.x};
+  int c = 0;
+  for (; c < max_chunks; ++c) {
+    const bool active = c < mc;
+    if (!__any(active)) break;  // wave-uniform: chains only get shorter
+    uint32_t tok[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j)
+      tok[j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * B + bi];
+    const uint64_t h2 = chunk_hash_sha256_wave(
+        h, tok, BS, sha_digest_word(ALGO), col, active, ShaWaveAny{});
+    h = active ? h2 : h;
+    if (live)
+      out[chain_out_index(row_major, lane, c, max_chunks, B)] =
+          active ? h : 0;
+  }
+  // the wave left early: its remaining slots are all unused
+  if (live)
+    for (; c < max_chunks; ++c)
+      out[chain_out_index(row_major, lane, c, max_chunks, B)] = 0;
+}
+
+// Row-major staging of the FNV chain: chunks per flush, u64 per staged
+// prompt row (one pad), dynamic LDS per workgroup.
 constexpr int CHAIN_STAGE_CHUNKS = 16;
 constexpr int CHAIN_STAGE_ROW = CHAIN_STAGE_CHUNKS + 1;
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -546,192 +590,108 @@ constexpr size_t chain_stage_bytes(int threads) {
   return (size_t)threads * CHAIN_STAGE_ROW * sizeof(uint64_t);
 }
 
-template <int BS, int ILP, int ALGO = ALGO_FNV64A>
-__global__ void k_hash_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
-                                const uint64_t* __restrict__ parents,  // [B]
-                                const int32_t* __restrict__ n_chunks,  // [B]
-                                int64_t B, int64_t L, int max_chunks,
-                                int row_major,
-                                uint64_t* __restrict__ out) {  // [maxC,B] or [B,maxC]
-  if constexpr (ALGO != ALGO_FNV64A) {
-    static_assert(ILP == 1, "the SHA chain runs one prompt per lane");
-    constexpr int NT = sha_tr_threads(BS);
-    __shared__ uint32_t sha_words[sha_tr_words(BS) * NT];
-    const int64_t lane = (int64_t)blockIdx.x * NT + threadIdx.x;
-    // no early return: idle lanes ride along (clamped loads, results
-    // discarded) so every wave-wide vote below sees whole waves
-    const bool live = lane < B;
-    const int64_t bi = live ? lane : 0;
-    uint64_t h = parents[bi];
-    const int mc = live ? n_chunks[bi] : 0;
-    ShaLdsCol<NT> col{sha_words + threadIdx.x};
-    int c = 0;
-    for (; c < max_chunks; ++c) {
-      const bool active = c < mc;
-      if (!__any(active)) break;  // wave-uniform: chains only get shorter
-      uint32_t tok[BS];
+// Row-major output: a store of one chunk's hashes straight from the
+// lanes is 64 separate 8-byte pieces, max_chunks * 8 bytes apart.  The
+// wave parks each chunk's hashes in LDS instead and, every
+// CHAIN_STAGE_CHUNKS chunks (and after the last), this writes each
+// prompt's 128 bytes as eight 16-byte stores from eight neighbouring
+// lanes: whole lines.
+// Layout [prompt][17] u64 (16 chunks + 1 pad, 136 B rows), by the LDS
+// bank model (ds_write_b64 and ds_read2_b64: bank = dword address mod
+// 32, conflicts within groups of 16 consecutive lanes):
+//  - write, lane p stores dwords 34p+2cc, +1: 34 = 2 mod 32, so 16
+//    lanes cover all 32 banks once;
+//  - read, lane l takes dwords 34(8g + l/8) + 4(l%8) + {0,1} and
+//    {2,3}: per access the 8 lanes of a row hit banks 4i, 4i+1 off the
+//    row's base, the group's other row is based 2 banks further on and
+//    fills the gaps.
+// Both are conflict-free.  One wave owns its region, and a wave's LDS
+// operations execute in order, so wavefront-scope fences (no
+// instructions, only compiler ordering) are all the synchronisation.
+// stage: this wave's [64][CHAIN_STAGE_ROW]; lane: global lane = prompt;
+// wl: lane within the wave; c: the chunk just staged.
+DEV void chain_flush_rows(const uint64_t* stage, uint64_t* __restrict__ out,
+                          int64_t lane, int wl, int c, int max_chunks,
+                          int64_t B) {
+  // flush chunks [c0, c0 + n): lane l writes chunks c0 + 2(l%8),
+  // +1 of prompt 8g + l/8 of this wave, g = 0..7
+  const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
+  const int c0 = c - cc;
+  const int n = cc + 1;
+  // rows start 16-byte aligned iff max_chunks is even; n is then
+  // even too.  Odd max_chunks keeps 8-byte stores.
+  const bool vec = (max_chunks & 1) == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int part2 = 2 * (wl & 7);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-      for (int j = 0; j < BS; ++j)
-        tok[j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * B + bi];
-      const uint64_t h2 = chunk_hash_sha256_wave(
-          h, tok, BS, sha_digest_word(ALGO), col, active, ShaWaveAny{});
-      h = active ? h2 : h;
-      if (live)
-        out[row_major ? (int64_t)lane * max_chunks + c
-                      : (int64_t)c * B + lane] = active ? h : 0;
-    }
-    // the wave left early: its remaining slots are all unused
-    if (live)
-      for (; c < max_chunks; ++c)
-        out[row_major ? (int64_t)lane * max_chunks + c
-                      : (int64_t)c * B + lane] = 0;
-    return;
-  }
-  const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  // Row-major output, ILP 1: a store of one chunk's hashes straight from
-  // the lanes is 64 separate 8-byte pieces, max_chunks * 8 bytes apart.
-  // The wave parks each chunk's hashes in LDS instead and, every
-  // CHAIN_STAGE_CHUNKS chunks, writes each prompt's 128 bytes as eight
-  // 16-byte stores from eight neighbouring lanes: whole lines.
-  // Layout [prompt][17] u64 (16 chunks + 1 pad, 136 B rows), by the LDS
-  // bank model (ds_write_b64 and ds_read2_b64: bank = dword address mod
-  // 32, conflicts within groups of 16 consecutive lanes):
-  //  - write, lane p stores dwords 34p+2cc, +1: 34 = 2 mod 32, so 16
-  //    lanes cover all 32 banks once;
-  //  - read, lane l takes dwords 34(8g + l/8) + 4(l%8) + {0,1} and
-  //    {2,3}: per access the 8 lanes of a row hit banks 4i, 4i+1 off the
-  //    row's base, the group's other row is based 2 banks further on and
-  //    fills the gaps.
-  // Both are conflict-free.  One wave owns its region, and a wave's LDS
-  // operations execute in order, so wavefront-scope fences (no
-  // instructions, only compiler ordering) are all the synchronisation.
-  extern __shared__ uint64_t chain_stage[];  // [waves][64][CHAIN_STAGE_ROW]
-  const int wl = threadIdx.x & 63;
-  uint64_t* stage =
-      chain_stage + (size_t)(threadIdx.x >> 6) * (64 * CHAIN_STAGE_ROW);
-  int64_t b[ILP];
-  uint64_t h[ILP];
-  int mc[ILP];
-  bool live[ILP];
-  // no early return here either: the wide-parent vote below needs whole
-  // waves, so lanes past L ride along like dead chains
-#pragma unroll
-  for (int i = 0; i < ILP; ++i) {
-    b[i] = lane + (int64_t)i * L;
-    live[i] = lane < L && b[i] < B;
-    h[i] = live[i] ? parents[b[i]] : 0;
-    mc[i] = live[i] ? n_chunks[b[i]] : 0;
-  }
-  for (int c = 0; c < max_chunks; ++c) {
-    uint32_t tok[ILP][BS];
-    // loads and hash bodies are UNCONDITIONAL (clamped addresses, dead
-    // chains compute garbage that a select discards): keeps the whole
-    // chunk step one basic block so the ILP chains actually interleave.
-#pragma unroll
-    for (int i = 0; i < ILP; ++i) {
-      const int64_t bi = live[i] ? b[i] : 0;
-#pragma unroll
-      for (int j = 0; j < BS; ++j)
-        tok[i][j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * B + bi];
-    }
-#pragma unroll
-    for (int i = 0; i < ILP; ++i) {
-      const bool active = live[i] && c < mc[i];
-      // Wave-uniform vote: every chain of the wave that still runs has a
-      // parent above 0xFFFFFFFF (after chunk 0 it is a 64-bit hash), so
-      // the parent item needs no selects.  A scalar branch, taken by the
-      // whole wave.  The ILP > 1 bodies stay one basic block and keep
-      // the generic parent item.
-      bool wide = false;
-      if constexpr (ILP == 1)
-        wide = __all(!active || h[i] > 0xFFFFFFFFull);
-      const uint64_t h2 = chunk_hash_fast(h[i], tok[i], BS, wide);
-      h[i] = active ? h2 : h[i];
-      // row_major writes the layout the fused-score kernel consumes,
-      // which saves a 128 MB/call transpose pass downstream.  Unused
-      // slots get their zero here: the caller hands in uninitialised
-      // memory.  With ILP > 1 the row-major stores stay scattered
-      // (stride maxC per lane).
-      const uint64_t val = active ? h[i] : 0;
-      if (ILP == 1 && row_major)
-        stage[wl * CHAIN_STAGE_ROW + (c & (CHAIN_STAGE_CHUNKS - 1))] = val;
-      else if (live[i])
-        out[row_major ? (int64_t)b[i] * max_chunks + c
-                      : (int64_t)c * B + b[i]] = val;
-    }
-    if constexpr (ILP == 1) {
-      const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
-      if (row_major && (cc == CHAIN_STAGE_CHUNKS - 1 || c == max_chunks - 1)) {
-        // flush chunks [c0, c0 + n): lane l writes chunks c0 + 2(l%8),
-        // +1 of prompt 8g + l/8 of this wave, g = 0..7
-        const int c0 = c - cc;
-        const int n = cc + 1;
-        // rows start 16-byte aligned iff max_chunks is even; n is then
-        // even too.  Odd max_chunks keeps 8-byte stores.
-        const bool vec = (max_chunks & 1) == 0 &&
-                         (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        const int part2 = 2 * (wl & 7);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-          const int r = g * 8 + (wl >> 3);
-          const int64_t pb = lane - wl + r;  // prompt of row r
-          const uint64_t* s = stage + r * CHAIN_STAGE_ROW + part2;
-          const uint64_t v0 = s[0];
-          const uint64_t v1 = s[1];
-          if (pb < B && part2 < n) {
-            uint64_t* o = out + pb * max_chunks + c0 + part2;
-            if (vec) {
-              *reinterpret_cast<u64x2*>(o) = u64x2{v0, v1};  // dwordx4
-            } else {
-              o[0] = v0;
-              if (part2 + 1 < n) o[1] = v1;
-            }
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int g = 0; g < 8; ++g) {
+    const int r = g * 8 + (wl >> 3);
+    const int64_t pb = lane - wl + r;  // prompt of row r
+    const uint64_t* s = stage + r * CHAIN_STAGE_ROW + part2;
+    const uint64_t v0 = s[0];
+    const uint64_t v1 = s[1];
+    if (pb < B && part2 < n) {
+      uint64_t* o = out + pb * max_chunks + c0 + part2;
+      if (vec) {
+        *reinterpret_cast<u64x2*>(o) = u64x2{v0, v1};  // dwordx4
+      } else {
+        o[0] = v0;
+        if (part2 + 1 < n) o[1] = v1;
       }
     }
   }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Double-buffered single-chain variant: chunk c+1's coalesced loads are
-// issued BEFORE chunk c's hash chain, so HBM latency hides under the
-// serial ALU work (the plain variant exposes ~full load latency at each
-// chunk boundary).  Token loop in chunk_hash_fast is force-unrolled so
-// the buffers stay in named registers (no gpr_idx, no vmcnt(0) drain).
 template <int BS>
-__global__ void k_hash_chain_tr_pf(const int32_t* __restrict__ tokens_t,
-                                   const uint64_t* __restrict__ parents,
-                                   const int32_t* __restrict__ n_chunks,
-                                   int64_t B, int64_t L, int max_chunks,
-                                   int row_major,
-                                   uint64_t* __restrict__ out) {
+__global__ void k_fnv_chain_tr(const int32_t* __restrict__ tokens_t,  // [T,B]
+                               const uint64_t* __restrict__ parents,  // [B]
+                               const int32_t* __restrict__ n_chunks,  // [B]
+                               int64_t B, int max_chunks, int row_major,
+                               uint64_t* __restrict__ out) {  // [maxC,B] or [B,maxC]
+  extern __shared__ uint64_t chain_stage[];  // [waves][64][CHAIN_STAGE_ROW]
   const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= L) return;
-  uint64_t h = parents[lane];
-  const int mc = n_chunks[lane];
-  uint32_t cur[BS], nxt[BS];
-#pragma unroll
-  for (int j = 0; j < BS; ++j)
-    cur[j] = (uint32_t)tokens_t[(int64_t)j * B + lane];
+  const int wl = threadIdx.x & 63;
+  uint64_t* stage =
+      chain_stage + (size_t)(threadIdx.x >> 6) * (64 * CHAIN_STAGE_ROW);
+  // no early return here either: the wide-parent vote below needs whole
+  // waves, so lanes past B ride along as chains of no chunks
+  const bool live = lane < B;
+  const int64_t bi = live ? lane : 0;
+  uint64_t h = parents[bi];
+  const int mc = live ? n_chunks[bi] : 0;
   for (int c = 0; c < max_chunks; ++c) {
-    if (c + 1 < max_chunks) {
+    // loads and the hash body are UNCONDITIONAL (clamped addresses, dead
+    // chains compute garbage that a select discards)
+    uint32_t tok[BS];
 #pragma unroll
-      for (int j = 0; j < BS; ++j)
-        nxt[j] = (uint32_t)tokens_t[(int64_t)((c + 1) * BS + j) * B + lane];
-    }
+    for (int j = 0; j < BS; ++j)
+      tok[j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * B + bi];
     const bool active = c < mc;
-    const uint64_t h2 = chunk_hash_fast(h, cur, BS);
+    // Wave-uniform vote: every chain of the wave that still runs has a
+    // parent above 0xFFFFFFFF (after chunk 0 it is a 64-bit hash), so
+    // the parent item needs no selects.  A scalar branch, taken by the
+    // whole wave.
+    const bool wide = __all(!active || h > 0xFFFFFFFFull);
+    const uint64_t h2 = chunk_hash_fast(h, tok, BS, wide);
     h = active ? h2 : h;
-    out[row_major ? (int64_t)lane * max_chunks + c
-                  : (int64_t)c * B + lane] = active ? h : 0;
-#pragma unroll
-    for (int j = 0; j < BS; ++j) cur[j] = nxt[j];
+    // row_major writes the layout the fused-score kernel consumes,
+    // which saves a 128 MB/call transpose pass downstream.  Unused
+    // slots get their zero here: the caller hands in uninitialised
+    // memory.
+    const uint64_t val = active ? h : 0;
+    const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
+    if (row_major)
+      stage[wl * CHAIN_STAGE_ROW + cc] = val;
+    else if (live)
+      out[chain_out_index(row_major, lane, c, max_chunks, B)] = val;
+    if (row_major && (cc == CHAIN_STAGE_CHUNKS - 1 || c == max_chunks - 1))
+      chain_flush_rows(stage, out, lane, wl, c, max_chunks, B);
   }
 }
 
@@ -743,7 +703,7 @@ __global__ void k_hash_chain_tr_pf(const int32_t* __restrict__ tokens_t,
 // fan out the per-block inserts.
 template <int ALGO>
 __global__ void k_apply_events(
-    DevTable v, const int64_t* __restrict__ tokens,
+    Table v, const int64_t* __restrict__ tokens,
     const int32_t* __restrict__ tok_off,     // [E+1]
     const uint64_t* __restrict__ ehashes,    // engine hashes, flat
     const int32_t* __restrict__ eh_off,      // [E+1]
@@ -767,41 +727,20 @@ __global__ void k_apply_events(
     const uint64_t* eh = ehashes + eh_off[e];
     const uint32_t model = (uint32_t)model_of[e];
     if (ev_type[e] == 1) {  // BlockRemoved
-      for (int i = lane; i < nh; i += 64) {
-        int64_t ei = dev_emap_find(v, eh[i], model);
-        if (ei < 0) continue;
-        uint64_t req = v.e_vals[ei];
-        int64_t slot = dev_table_find(v, req, model);
-        if (slot < 0) continue;  // emap retained (see cpu_evict note)
-        uint32_t* p = v.pods + slot * v.pods_per_key;
-        for (int k = 0; k < v.pods_per_key; ++k)
-          atomicCAS(&p[k], pod_entry[e], 0u);
-        bool empty = true;
-        for (int k = 0; k < v.pods_per_key; ++k)
-          if (p[k] != 0) { empty = false; break; }
-        if (empty) atomicOr(&v.meta[slot], META_TOMB);
-      }
+      for (int i = lane; i < nh; i += 64)
+        dev_remove_pods(v, eh[i], model, &pod_entry[e], 1);
       __builtin_amdgcn_wave_barrier();
       continue;
     }
     // BlockStored: lane 0 resolves parent + streams the request chain.
-    const int n_tok = tok_off[e + 1] - tok_off[e];
-    const int n_chunks = n_tok / block_size;
-    // Engine-hash count must match the token-derived chain length; the
-    // reference Add() (and this repo's CPU digest path) rejects the whole
-    // event on mismatch - dropping here keeps CPU and GPU replicas
-    // convergent on malformed streams. (Uniform per wave: n_chunks/nh
-    // are scalar per event.)
-    if (n_chunks != nh) continue;
+    // (The mismatch drop is uniform per wave: scalar per event.)
+    const int n_chunks = event_chain_len(tok_off, eh_off, e, block_size);
+    if (n_chunks < 0) continue;
     uint64_t* req = req_scratch + eh_off[e];
     if (lane == 0) {
-      uint64_t parent = init_hash;
-      if (has_parent[e]) {
-        int64_t ei = dev_emap_find(v, parents[e], model);
-        if (ei >= 0) parent = v.e_vals[ei];
-      }
       const int64_t* t0 = tokens + tok_off[e];
-      uint64_t h = parent;
+      uint64_t h =
+          dev_event_parent(v, has_parent, parents, model_of, e, init_hash);
       for (int c = 0; c < n_chunks; ++c) {
         h = chain_link<ALGO>(h, t0 + (int64_t)c * block_size, block_size);
         req[c] = h;
@@ -809,15 +748,9 @@ __global__ void k_apply_events(
     }
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
-    const int n_ins = n_chunks;
-    for (int i = lane; i < n_ins; i += 64) {
-      dev_emap_put(v, eh[i], model, remap_hash(req[i]));
-      if (num_shards > 1 &&
-          (int)(remap_hash(req[i]) % (uint64_t)num_shards) != shard_id)
-        continue;
-      int64_t slot = dev_table_put(v, req[i], model, epoch);
-      dev_pod_set_add(v, slot, pod_entry[e], epoch);
-    }
+    for (int i = lane; i < n_chunks; i += 64)
+      dev_store_block(v, eh[i], req[i], model, &pod_entry[e], 1, epoch,
+                      shard_id, num_shards, 1);
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -874,7 +807,7 @@ DEV int64_t dev_bmap_find(const uint64_t* __restrict__ bkeys,
 // engine map (cross-batch), else the chain root.
 template <int ALGO>
 __global__ void k_event_chains(
-    DevTable v, const int64_t* __restrict__ tokens,
+    Table v, const int64_t* __restrict__ tokens,
     const int32_t* __restrict__ tok_off, const uint64_t* __restrict__ ehashes,
     const int32_t* __restrict__ eh_off, const uint64_t* __restrict__ parents,
     const uint8_t* __restrict__ has_parent, const uint8_t* __restrict__ ev_type,
@@ -890,26 +823,16 @@ __global__ void k_event_chains(
   const int grp_first_block = eh_off[e_begin];
   for (int e = e_begin; e < e_end; ++e) {
     if (ev_type[e] == 1) continue;  // removals have no chain
-    const int nh = eh_off[e + 1] - eh_off[e];
-    const int n_chunks = (tok_off[e + 1] - tok_off[e]) / block_size;
-    if (n_chunks != nh) continue;  // drop mismatched event (see
-                                   // k_apply_events; k_event_inserts
-                                   // applies the same guard)
-    uint64_t parent = init_hash;
-    if (has_parent[e]) {
-      int64_t bi = dev_bmap_find(bkeys, bvals, bmask, parents[e]);
-      if (bi >= grp_first_block && bi < eh_off[e]) {
-        parent = req_scratch[bi];  // earlier event of this group
-      } else {
-        int64_t ei = dev_emap_find(v, parents[e],
-                                   (uint32_t)model_of[e]);
-        if (ei >= 0) parent = v.e_vals[ei];
-      }
-    }
+    const int n_chunks = event_chain_len(tok_off, eh_off, e, block_size);
+    if (n_chunks < 0) continue;
+    const int64_t bi =
+        has_parent[e] ? dev_bmap_find(bkeys, bvals, bmask, parents[e]) : -1;
     const int64_t* t0 = tokens + tok_off[e];
-    uint64_t h = parent;
-    const int n_ins = min(n_chunks, nh);
-    for (int c = 0; c < n_ins; ++c) {
+    uint64_t h = bi >= grp_first_block && bi < eh_off[e]
+                     ? req_scratch[bi]  // earlier event of this group
+                     : dev_event_parent(v, has_parent, parents, model_of, e,
+                                        init_hash);
+    for (int c = 0; c < n_chunks; ++c) {
       h = chain_link<ALGO>(h, t0 + (int64_t)c * block_size, block_size);
       req_scratch[eh_off[e] + c] = h;
     }
@@ -940,7 +863,7 @@ __global__ void k_transpose_ev_tokens(const int32_t* __restrict__ flat,
     out[(int64_t)i * E + e] = flat[tok_off[e] + i];
 }
 
-// Read-path staging for k_hash_chain_tr: flat ragged tokens (int64 or
+// Read-path staging for the chain kernels: flat ragged tokens (int64 or
 // int32, narrowed to their low 32 bits as hash_chain_batch does) ->
 // transposed int32 image [T = max_chunks * block_size][B].  A read batch
 // is ~128 MB of image (4096 prompts x 8192 tokens), so unlike the event
@@ -1001,7 +924,7 @@ __global__ void __launch_bounds__(256) k_stage_ragged_tokens(
 
 template <int ALGO>
 __global__ void k_event_chains_ev(
-    DevTable v, const int32_t* __restrict__ tokens_t,  // [maxT, E]
+    Table v, const int32_t* __restrict__ tokens_t,  // [maxT, E]
     const int32_t* __restrict__ tok_off, const uint64_t* __restrict__ ehashes,
     const int32_t* __restrict__ eh_off, const uint64_t* __restrict__ parents,
     const uint8_t* __restrict__ has_parent, const uint8_t* __restrict__ ev_type,
@@ -1010,16 +933,9 @@ __global__ void k_event_chains_ev(
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
   if (ev_type[e] == 1) return;  // removals have no chain
-  const int nh = eh_off[e + 1] - eh_off[e];
-  KVIDX_ASSERT(nh >= 0 && tok_off[e + 1] >= tok_off[e]);
-  const int n_chunks = (tok_off[e + 1] - tok_off[e]) / block_size;
-  if (n_chunks != nh) return;  // drop mismatched event (see k_apply_events)
-  uint64_t parent = init_hash;
-  if (has_parent[e]) {
-    int64_t ei = dev_emap_find(v, parents[e], (uint32_t)model_of[e]);
-    if (ei >= 0) parent = v.e_vals[ei];
-  }
-  uint64_t h = parent;
+  const int n_chunks = event_chain_len(tok_off, eh_off, e, block_size);
+  if (n_chunks < 0) return;
+  uint64_t h = dev_event_parent(v, has_parent, parents, model_of, e, init_hash);
   uint32_t tok[64];  // block_size <= 64
   for (int c = 0; c < n_chunks; ++c) {
     for (int j = 0; j < block_size; ++j)
@@ -1031,7 +947,7 @@ __global__ void k_event_chains_ev(
 
 // Phase B: one thread per block applies its insert/removal.
 __global__ void k_event_inserts(
-    DevTable v, const uint64_t* __restrict__ ehashes,
+    Table v, const uint64_t* __restrict__ ehashes,
     const int32_t* __restrict__ eh_off, const int32_t* __restrict__ ev_of,
     const uint8_t* __restrict__ ev_type, const int32_t* __restrict__ tok_off,
     const uint32_t* __restrict__ pod_entry,
@@ -1043,433 +959,88 @@ __global__ void k_event_inserts(
   const int e = ev_of[i];
   const uint32_t model = (uint32_t)model_of[e];
   if (ev_type[e] == 1) {  // BlockRemoved
-    int64_t ei = dev_emap_find(v, ehashes[i], model);
-    if (ei < 0) return;
-    uint64_t req = v.e_vals[ei];
-    int64_t slot = dev_table_find(v, req, model);
-    if (slot < 0) return;  // emap retained (see cpu_evict note)
-    uint32_t* p = v.pods + slot * v.pods_per_key;
-    for (int k = 0; k < v.pods_per_key; ++k)
-      atomicCAS(&p[k], pod_entry[e], 0u);
-    bool empty = true;
-    for (int k = 0; k < v.pods_per_key; ++k)
-      if (p[k] != 0) { empty = false; break; }
-    if (empty) atomicOr(&v.meta[slot], META_TOMB);
+    dev_remove_pods(v, ehashes[i], model, &pod_entry[e], 1);
     return;
   }
-  // BlockStored: dropped entirely when the engine-hash count mismatches
-  // the token-derived chain (same guard as k_event_chains/k_apply_events)
-  const int local = (int)(i - eh_off[e]);
-  const int n_chunks = (tok_off[e + 1] - tok_off[e]) / block_size;
-  if (n_chunks != eh_off[e + 1] - eh_off[e]) return;
-  if (local >= n_chunks) return;
-  const uint64_t req = req_scratch[i];
-  dev_emap_put(v, ehashes[i], model, remap_hash(req));
-  if (num_shards > 1 &&
-      (int)(remap_hash(req) % (uint64_t)num_shards) != shard_id)
-    return;
-  int64_t slot = dev_table_put(v, req, model, epoch);
-  dev_pod_set_add(v, slot, pod_entry[e], epoch);
+  // BlockStored: block i is one of the event's eh_off[e + 1] - eh_off[e]
+  // engine hashes, which a kept event has one chunk each for
+  if (event_chain_len(tok_off, eh_off, e, block_size) < 0) return;
+  dev_store_block(v, ehashes[i], req_scratch[i], model, &pod_entry[e], 1,
+                  epoch, shard_id, num_shards, 1);
 }
 
 // ---------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------
 
-static DevTable dev_view(at::Tensor& keys, at::Tensor& meta, at::Tensor& stamp,
-                         at::Tensor& pods, at::Tensor& e_keys,
-                         at::Tensor& e_meta, at::Tensor& e_vals,
-                         int64_t pods_per_key) {
-  TORCH_CHECK(keys.is_cuda(), "table must live on the GPU");
-  int64_t cap = keys.numel();
-  TORCH_CHECK((cap & (cap - 1)) == 0, "capacity must be a power of two");
-  DevTable v;
-  v.keys = reinterpret_cast<uint64_t*>(keys.data_ptr<int64_t>());
-  v.meta = reinterpret_cast<uint32_t*>(meta.data_ptr<int32_t>());
-  v.stamp = stamp.data_ptr<int32_t>();
-  v.pods = reinterpret_cast<uint32_t*>(pods.data_ptr<int32_t>());
-  v.e_keys = reinterpret_cast<uint64_t*>(e_keys.data_ptr<int64_t>());
-  v.e_meta = reinterpret_cast<uint32_t*>(e_meta.data_ptr<int32_t>());
-  v.e_vals = reinterpret_cast<uint64_t*>(e_vals.data_ptr<int64_t>());
-  v.cap_mask = (uint64_t)cap - 1;
-  v.pods_per_key = (int)pods_per_key;
-  return v;
-}
-
-#define U64P(t) reinterpret_cast<const uint64_t*>((t).data_ptr<int64_t>())
 #define STREAM at::cuda::getCurrentCUDAStream().stream()
 
-void gpu_insert(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-                at::Tensor e_vals, int64_t pods_per_key,
-                at::Tensor engine_hashes, at::Tensor request_hashes,
-                int64_t model_id, at::Tensor pod_entries, int64_t epoch,
-                int64_t shard_id, int64_t num_shards, int64_t emap_write) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
-  int64_t n = engine_hashes.numel();
-  if (n == 0) return;
-  int threads = 256;
-  int blocks = (int)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(k_insert, dim3(blocks), dim3(threads), 0, STREAM, v,
-                     U64P(engine_hashes), U64P(request_hashes), n,
-                     (uint32_t)model_id,
-                     reinterpret_cast<const uint32_t*>(
-                         pod_entries.data_ptr<int32_t>()),
-                     (int)pod_entries.numel(), (int32_t)epoch,
-                     (int)shard_id, (int)num_shards, (int)emap_write);
+// kernel<<<ceil(n / 256), 256>>>(args...) on the current stream: the
+// shape of every thread-per-item kernel here.
+template <typename Kern, typename... Args>
+static void launch_1d(Kern kernel, int64_t n, Args... args) {
+  constexpr int threads = 256;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + threads - 1) / threads)),
+                     dim3(threads), 0, STREAM, args...);
 }
 
-void gpu_compact(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                 at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-                 at::Tensor e_vals, int64_t pods_per_key,
-                 at::Tensor n_keys, at::Tensor n_meta, at::Tensor n_stamp,
-                 at::Tensor n_pods, at::Tensor n_e_keys, at::Tensor n_e_meta,
-                 at::Tensor n_e_vals) {
-  auto ov = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                     pods_per_key);
-  auto nv = dev_view(n_keys, n_meta, n_stamp, n_pods, n_e_keys, n_e_meta,
-                     n_e_vals, pods_per_key);
-  int64_t cap = keys.numel();
-  int threads = 256;
-  int blocks = (int)((cap + threads - 1) / threads);
-  hipLaunchKernelGGL(k_compact_main, dim3(blocks), dim3(threads), 0, STREAM,
-                     ov, nv, cap);
-  hipLaunchKernelGGL(k_compact_emap, dim3(blocks), dim3(threads), 0, STREAM,
-                     ov, nv, cap);
+static const uint64_t* filter_ptr(const at::Tensor& filter_words) {
+  return filter_words.numel() > 0 ? u64p(filter_words) : nullptr;
 }
 
-void gpu_evict(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-               at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-               at::Tensor e_vals, int64_t pods_per_key,
-               at::Tensor engine_hashes, int64_t model_id,
-               at::Tensor pod_entries) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
-  int64_t n = engine_hashes.numel();
-  if (n == 0) return;
-  int threads = 256;
-  int blocks = (int)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(k_evict, dim3(blocks), dim3(threads), 0, STREAM, v,
-                     U64P(engine_hashes), n, (uint32_t)model_id,
-                     reinterpret_cast<const uint32_t*>(
-                         pod_entries.data_ptr<int32_t>()),
-                     (int)pod_entries.numel());
+// The fused-score kernels hold a prompt's masks in LDS: up to 16 pod
+// words, 64 KB.  gpu_score_flat_tokens asks fused_score_fits to choose
+// its route; the launcher refuses what does not fit.
+static size_t fused_score_lds_bytes(int64_t max_k, int64_t n_tiers,
+                                    int64_t W) {
+  return (size_t)max_k * n_tiers * W * sizeof(uint64_t);
+}
+static bool fused_score_fits(int64_t max_k, int64_t n_tiers, int64_t W) {
+  return W <= 16 && fused_score_lds_bytes(max_k, n_tiers, W) <= 64 * 1024;
 }
 
-std::vector<at::Tensor> gpu_get_request_keys(
-    at::Tensor keys, at::Tensor meta, at::Tensor stamp, at::Tensor pods,
-    at::Tensor e_keys, at::Tensor e_meta, at::Tensor e_vals,
-    int64_t pods_per_key, at::Tensor engine_hashes, int64_t model_id) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
-  int64_t n = engine_hashes.numel();
-  auto found = at::zeros({n}, engine_hashes.options().dtype(at::kByte));
-  auto out = at::zeros({n}, engine_hashes.options());
-  if (n == 0) return {found, out};
-  int threads = 256;
-  int blocks = (int)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(k_get_request_keys, dim3(blocks), dim3(threads), 0,
-                     STREAM, v, U64P(engine_hashes), n, (uint32_t)model_id,
-                     found.data_ptr<uint8_t>(),
-                     reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
-  return {found, out};
-}
-
-std::vector<at::Tensor> gpu_lookup(at::Tensor keys, at::Tensor meta,
-                                   at::Tensor stamp, at::Tensor pods,
-                                   at::Tensor e_keys, at::Tensor e_meta,
-                                   at::Tensor e_vals, int64_t pods_per_key,
-                                   at::Tensor request_hashes, int64_t model_id,
-                                   at::Tensor filter_words, int64_t num_pods,
-                                   int64_t epoch, int64_t shard_id,
-                                   int64_t num_shards, int64_t n_tiers) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
-  int64_t K = request_hashes.numel();
-  int64_t W = (num_pods + 63) / 64;
-  bool has_filter = filter_words.numel() > 0;
-  if (n_tiers < 1) n_tiers = 1;
-  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
-  auto found = at::zeros({K}, request_hashes.options().dtype(at::kByte));
-  // tier planes sized by the registered tier count (see cpu_lookup)
-  auto masks = at::zeros({K, n_tiers, W}, request_hashes.options());
-  if (K == 0) return {found, masks};
-  int threads = 256;
-  int blocks = (int)((K + threads - 1) / threads);
-  hipLaunchKernelGGL(
-      k_lookup_masks, dim3(blocks), dim3(threads), 0, STREAM, v,
-      U64P(request_hashes), K, (uint32_t)model_id,
-      has_filter ? U64P(filter_words) : nullptr, has_filter ? 1 : 0,
-      (int)num_pods, (int)W, (int32_t)epoch, (int)shard_id, (int)num_shards,
-      (int)n_tiers, found.data_ptr<uint8_t>(),
-      reinterpret_cast<unsigned long long*>(masks.data_ptr<int64_t>()));
-  return {found, masks};
-}
-
-at::Tensor gpu_fused_score(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                           at::Tensor pods, at::Tensor e_keys,
-                           at::Tensor e_meta, at::Tensor e_vals,
-                           int64_t pods_per_key, at::Tensor hashes,
-                           at::Tensor offsets, int64_t model_id,
-                           at::Tensor filter_words, at::Tensor weights,
-                           int64_t num_pods, int64_t epoch, int64_t max_k,
-                           int64_t n_tiers) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
-  int64_t B = offsets.numel() - 1;
-  int64_t W = (num_pods + 63) / 64;
+// One workgroup per prompt.  where...: the kernel arguments between the
+// hashes and the model id, which say where prompt b's keys lie.
+template <typename Kern, typename... Where>
+static at::Tensor launch_fused_score(Kern kernel, const Table& v, int64_t B,
+                                     const at::Tensor& hashes,
+                                     int64_t model_id,
+                                     const at::Tensor& filter_words,
+                                     const at::Tensor& weights,
+                                     int64_t num_pods, int64_t epoch,
+                                     int64_t max_k, int64_t n_tiers,
+                                     Where... where) {
+  int64_t W = pod_words(num_pods);
   TORCH_CHECK(W <= 16, "fused score supports up to 1024 pods");
-  if (n_tiers < 1) n_tiers = 1;
-  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
-  size_t lds = (size_t)max_k * n_tiers * W * sizeof(uint64_t);
-  TORCH_CHECK(lds <= 64 * 1024,
+  n_tiers = clamp_tiers(n_tiers);
+  TORCH_CHECK(fused_score_fits(max_k, n_tiers, W),
               "fused score LDS overflow: reduce keys per prompt or pods");
-  bool has_filter = filter_words.numel() > 0;
-  auto scores = at::zeros({B, num_pods},
-                          hashes.options().dtype(at::kFloat));
+  auto scores = at::zeros({B, num_pods}, hashes.options().dtype(at::kFloat));
   if (B == 0) return scores;
-  hipLaunchKernelGGL(
-      k_fused_score, dim3((int)B), dim3(256), lds, STREAM, v, U64P(hashes),
-      offsets.data_ptr<int32_t>(), (uint32_t)model_id,
-      has_filter ? U64P(filter_words) : nullptr, has_filter ? 1 : 0,
-      weights.data_ptr<float>(), (int)num_pods, (int)W, (int32_t)epoch,
-      (int)n_tiers, scores.data_ptr<float>());
+  const uint64_t* filter = filter_ptr(filter_words);
+  hipLaunchKernelGGL(kernel, dim3((int)B), dim3(256),
+                     fused_score_lds_bytes(max_k, n_tiers, W), STREAM, v,
+                     (const uint64_t*)u64p(hashes), where...,
+                     (uint32_t)model_id, filter, filter ? 1 : 0,
+                     weights.data_ptr<float>(), (int)num_pods, (int)W,
+                     (int32_t)epoch, (int)n_tiers, scores.data_ptr<float>());
   return scores;
 }
 
-at::Tensor gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
-                                at::Tensor weights, int64_t num_pods) {
-  int64_t B = offsets.numel() - 1;
-  int64_t W = (num_pods + 63) / 64;
-  TORCH_CHECK(W <= 64, "score_from_masks supports up to 4096 pods");
-  TORCH_CHECK(masks.dim() == 3, "masks must be [Ktot, T, W]");
-  int64_t T = masks.size(1);  // tier planes, sized by the lookup
-  auto scores = at::zeros({B, num_pods}, masks.options().dtype(at::kFloat));
-  if (B == 0) return scores;
-  int wgroups = (int)((W + 15) / 16);
-  hipLaunchKernelGGL(
-      k_score_from_masks, dim3((int)B, wgroups), dim3(64), 0, STREAM,
-      reinterpret_cast<const unsigned long long*>(masks.data_ptr<int64_t>()),
-      offsets.data_ptr<int32_t>(), weights.data_ptr<float>(), (int)T,
-      (int)num_pods, (int)W, scores.data_ptr<float>());
-  return scores;
-}
-
-// Runs f(std::integral_constant<int, ALGO>) for a native chain algo id
-// (0 fnv-64a, 1 sha256-cbor-64, 2 sha256-cbor-64-low): the id picks a
-// kernel instantiation on the host, never a branch inside a kernel.
+// Runs f(std::integral_constant<int, BS>) for a block size the transposed
+// chain kernels are built for.
 template <typename F>
-static void dispatch_algo(int64_t algo, F&& f) {
-  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
-  switch (algo) {
-    case ALGO_SHA256_HI:
-      f(std::integral_constant<int, ALGO_SHA256_HI>{});
-      break;
-    case ALGO_SHA256_LOW:
-      f(std::integral_constant<int, ALGO_SHA256_LOW>{});
-      break;
+static void dispatch_chain_block_size(int64_t block_size, F&& f) {
+  switch (block_size) {
+    case 4:  f(std::integral_constant<int, 4>{});  break;
+    case 8:  f(std::integral_constant<int, 8>{});  break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
     default:
-      f(std::integral_constant<int, ALGO_FNV64A>{});
-      break;
+      TORCH_CHECK(false, "hash_chain_tr supports block sizes 4/8/16/32/64; "
+                         "use gpu_hash_chain for other sizes");
   }
-}
-
-std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
-                                       at::Tensor parents,
-                                       int64_t block_size, int64_t algo) {
-  TORCH_CHECK(tokens.is_cuda());
-  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
-  int64_t B = parents.numel();
-  auto chunk_off_cpu = at::zeros({B + 1}, at::kLong);
-  {
-    auto off_cpu = tok_off.to(at::kCPU);
-    const int64_t* offp = off_cpu.data_ptr<int64_t>();
-    int64_t* cop = chunk_off_cpu.data_ptr<int64_t>();
-    for (int64_t b = 0; b < B; ++b)
-      cop[b + 1] = cop[b] + (offp[b + 1] - offp[b]) / block_size;
-  }
-  auto chunk_off = chunk_off_cpu.to(tokens.device());
-  int64_t total = chunk_off_cpu.data_ptr<int64_t>()[B];
-  auto out = at::empty({total}, tokens.options());
-  if (B == 0) return {out, chunk_off};
-  int threads = 256;
-  int blocks = (int)((B + threads - 1) / threads);
-  dispatch_algo(algo, [&](auto A) {
-    hipLaunchKernelGGL(k_hash_chain<decltype(A)::value>, dim3(blocks),
-                       dim3(threads), 0, STREAM, tokens.data_ptr<int64_t>(),
-                       tok_off.data_ptr<int64_t>(), U64P(parents),
-                       chunk_off.data_ptr<int64_t>(), B, (int)block_size,
-                       reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
-  });
-  return {out, chunk_off};
-}
-
-// tokens_t: int32 [T, B] (transposed); parents int64 [B]; n_chunks
-// int32 [B].  Returns out int64 [max_chunks, B] (transposed hashes).
-at::Tensor gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
-                             at::Tensor n_chunks, int64_t block_size,
-                             int64_t max_chunks, int64_t ilp,
-                             int64_t row_major, int64_t algo) {
-  TORCH_CHECK(tokens_t.is_cuda() && tokens_t.dtype() == at::kInt);
-  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
-  TORCH_CHECK(tokens_t.dim() == 2, "tokens_t must be [T, B]");
-  int64_t B = tokens_t.size(1);
-  TORCH_CHECK(parents.numel() == B && n_chunks.numel() == B);
-  // row_major=1: out is [B, max_chunks] (what the fused-score kernel
-  // consumes directly - no transpose pass); default [max_chunks, B].
-  // Not cleared: the kernels write every slot, a zero where
-  // c >= n_chunks[b].  Keep it so.  A fill kernel in front of the chain
-  // call costs only tens of µs, but with two kernels per call on the
-  // read path's side stream the runtime keeps falling back to running
-  // that stream and the score stream one after the other (call time
-  // 1.2 -> 2.7 ms, flipping between and within processes; measured
-  // with only this line changed, profiles/r04_fnv_chain.md).
-  auto out = at::empty(row_major ? std::initializer_list<int64_t>{B, max_chunks}
-                                 : std::initializer_list<int64_t>{max_chunks, B},
-                       parents.options());
-  if (B == 0 || max_chunks == 0) return out;
-  TORCH_CHECK(tokens_t.size(0) >= max_chunks * block_size,
-              "tokens_t has fewer rows than max_chunks * block_size");
-  auto tokens_c = tokens_t.contiguous();
-  if (algo != ALGO_FNV64A) {
-    // SHA-256 chains: one prompt per lane (ilp is an FNV tuning knob and
-    // is ignored), workgroup width set by the LDS payload columns.
-    auto launch_sha = [&](auto kern, int threads) {
-      int blocks = (int)((B + threads - 1) / threads);
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, STREAM,
-                         tokens_c.data_ptr<int32_t>(), U64P(parents),
-                         n_chunks.data_ptr<int32_t>(), B, B, (int)max_chunks,
-                         (int)row_major,
-                         reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
-    };
-    dispatch_algo(algo, [&](auto A) {
-      constexpr int AL = decltype(A)::value;
-      if constexpr (AL != ALGO_FNV64A) {
-        switch (block_size) {
-          case 4:  launch_sha(k_hash_chain_tr<4, 1, AL>, sha_tr_threads(4)); break;
-          case 8:  launch_sha(k_hash_chain_tr<8, 1, AL>, sha_tr_threads(8)); break;
-          case 16: launch_sha(k_hash_chain_tr<16, 1, AL>, sha_tr_threads(16)); break;
-          case 32: launch_sha(k_hash_chain_tr<32, 1, AL>, sha_tr_threads(32)); break;
-          case 64: launch_sha(k_hash_chain_tr<64, 1, AL>, sha_tr_threads(64)); break;
-          default:
-            TORCH_CHECK(false, "hash_chain_tr supports block sizes "
-                               "4/8/16/32/64; use gpu_hash_chain for other "
-                               "sizes");
-        }
-      }
-    });
-    return out;
-  }
-  // ILP puts several chains on one lane.  Sweep on MI355X
-  // (profiles/r01_chain_sweep.md): ILP>1 always loses - a lone wave is
-  // issue-bound, so x chains per lane cost close to x times the time
-  // whether or not they interleave.  Default 1.
-  int64_t want_ilp = ilp;
-  if (want_ilp <= 0) want_ilp = 1;
-  int64_t L = (B + want_ilp - 1) / want_ilp;  // lanes
-  // One-wave workgroups: B / 64 waves spread over all CUs before any CU
-  // gets a second one, where 256-thread workgroups put four waves on
-  // each of a quarter as many CUs.  Measured (profiles/r04_fnv_chain.md):
-  // alone, the row-major call is 8 % shorter and the transposed one the
-  // same; beside the score kernel the chain gains what the score kernel
-  // loses, and the chain is the longer stream, so the read call gets
-  // shorter.  A raised wave priority (s_setprio 1 at kernel entry) was
-  // tried with either shape and changed nothing measurable.  Measured
-  // again with row-major output staged through LDS
-  // (profiles/r05_score_walk.md): the two widths give the same call
-  // time, 64 is 0.005..0.008 ms shorter alone; 64 stays.
-  int threads = 64;
-  int blocks = (int)((L + threads - 1) / threads);
-  auto launch = [&](auto kern, size_t lds = 0) {
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, STREAM,
-                       tokens_c.data_ptr<int32_t>(), U64P(parents),
-                       n_chunks.data_ptr<int32_t>(), B, L, (int)max_chunks,
-                       (int)row_major,
-                       reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()));
-  };
-  bool done = false;
-  if (block_size == 16) {
-    done = true;
-    // Measured (profiles/r01_chain_sweep.md): the plain single-chain
-    // kernel with the force-unrolled token loop wins at every batch
-    // vs the explicit double-buffer prefetch variant - the prefetch's
-    // register moves cost more than the load latency they hide once the
-    // unroll removed the gpr_idx waits. (The original pf A/B runs also
-    // had a dispatch bug that gave pf 1/8 the lanes, flattering it 8x;
-    // the verdict only strengthens with the fix.)
-    switch (want_ilp) {
-      case 2: launch(k_hash_chain_tr<16, 2>); break;
-      case 8:  // A/B: prefetch variant is one lane per prompt (no ILP)
-        L = B;
-        blocks = (int)((L + threads - 1) / threads);
-        launch(k_hash_chain_tr_pf<16>);
-        break;
-      case 4: launch(k_hash_chain_tr<16, 4>); break;
-      default:  // the read path's kernel; row-major output stages in LDS
-        launch(k_hash_chain_tr<16, 1>,
-               row_major ? chain_stage_bytes(threads) : 0);
-        break;
-    }
-  }
-  if (!done) {
-    int fixed_ilp = block_size == 64 ? 2 : 4;
-    L = (B + fixed_ilp - 1) / fixed_ilp;
-    blocks = (int)((L + threads - 1) / threads);
-    switch (block_size) {
-      case 32: launch(k_hash_chain_tr<32, 4>); break;
-      case 64: launch(k_hash_chain_tr<64, 2>); break;
-      case 4:  launch(k_hash_chain_tr<4, 4>);  break;
-      case 8:  launch(k_hash_chain_tr<8, 4>);  break;
-      default:
-        TORCH_CHECK(false, "hash_chain_tr supports block sizes 4/8/16/32/64;"
-                           " use gpu_hash_chain for other sizes");
-    }
-  }
-  return out;
-}
-
-// gpu_fused_score over the padded rows that gpu_hash_chain_tr(row_major=1)
-// returns: hashes int64 [B, stride], n_keys int32 [B] on the device.
-at::Tensor gpu_fused_score_rows(at::Tensor keys, at::Tensor meta,
-                                at::Tensor stamp, at::Tensor pods,
-                                at::Tensor e_keys, at::Tensor e_meta,
-                                at::Tensor e_vals, int64_t pods_per_key,
-                                at::Tensor hashes, at::Tensor n_keys,
-                                int64_t model_id, at::Tensor filter_words,
-                                at::Tensor weights, int64_t num_pods,
-                                int64_t epoch, int64_t max_k,
-                                int64_t n_tiers) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
-  TORCH_CHECK(hashes.is_cuda() && hashes.dtype() == at::kLong &&
-                  hashes.dim() == 2 && hashes.is_contiguous(),
-              "hashes must be a contiguous int64 [B, stride] device tensor");
-  TORCH_CHECK(n_keys.is_cuda() && n_keys.dtype() == at::kInt &&
-                  n_keys.is_contiguous(),
-              "n_keys must be a contiguous int32 device tensor");
-  int64_t B = hashes.size(0);
-  int64_t stride = hashes.size(1);
-  TORCH_CHECK(n_keys.numel() == B, "n_keys must have one entry per row");
-  TORCH_CHECK(max_k <= stride, "max_k exceeds the row length");
-  int64_t W = (num_pods + 63) / 64;
-  TORCH_CHECK(W <= 16, "fused score supports up to 1024 pods");
-  if (n_tiers < 1) n_tiers = 1;
-  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
-  size_t lds = (size_t)max_k * n_tiers * W * sizeof(uint64_t);
-  TORCH_CHECK(lds <= 64 * 1024,
-              "fused score LDS overflow: reduce keys per prompt or pods");
-  bool has_filter = filter_words.numel() > 0;
-  auto scores = at::zeros({B, num_pods},
-                          hashes.options().dtype(at::kFloat));
-  if (B == 0) return scores;
-  hipLaunchKernelGGL(
-      k_fused_score_rows, dim3((int)B), dim3(256), lds, STREAM, v,
-      U64P(hashes), n_keys.data_ptr<int32_t>(), stride, (uint32_t)model_id,
-      has_filter ? U64P(filter_words) : nullptr, has_filter ? 1 : 0,
-      weights.data_ptr<float>(), (int)num_pods, (int)W, (int32_t)epoch,
-      (int)n_tiers, scores.data_ptr<float>());
-  return scores;
 }
 
 // Host half of the ragged staging: what the offsets say about a batch.
@@ -1531,24 +1102,258 @@ static std::vector<at::Tensor> stage_ragged(const RaggedPlan& p,
   int64_t pt = (p.B + STAGE_TILE - 1) / STAGE_TILE;
   TORCH_CHECK(pt <= 65535, "too many prompts in one batch");
   dim3 grid((unsigned)((T + STAGE_TILE - 1) / STAGE_TILE), (unsigned)pt);
+  auto launch = [&](auto* flat) {
+    using TokT = std::remove_const_t<std::remove_pointer_t<decltype(flat)>>;
+    hipLaunchKernelGGL(k_stage_ragged_tokens<TokT>, grid, dim3(256), 0, STREAM,
+                       flat, i32p(tok_off), i32p(n_chunks), p.B, T,
+                       (int)block_size, i32p(out));
+  };
   if (tok.dtype() == at::kLong)
-    hipLaunchKernelGGL(k_stage_ragged_tokens<int64_t>, grid, dim3(256), 0,
-                       STREAM, tok.data_ptr<int64_t>(),
-                       tok_off.data_ptr<int32_t>(),
-                       n_chunks.data_ptr<int32_t>(), p.B, T, (int)block_size,
-                       out.data_ptr<int32_t>());
+    launch(tok.data_ptr<int64_t>());
   else
-    hipLaunchKernelGGL(k_stage_ragged_tokens<int32_t>, grid, dim3(256), 0,
-                       STREAM, tok.data_ptr<int32_t>(),
-                       tok_off.data_ptr<int32_t>(),
-                       n_chunks.data_ptr<int32_t>(), p.B, T, (int)block_size,
-                       out.data_ptr<int32_t>());
+    launch(tok.data_ptr<int32_t>());
   return {out, n_chunks};
 }
 
-std::vector<at::Tensor> gpu_stage_ragged_tokens(at::Tensor tokens,
-                                                at::Tensor offsets,
-                                                int64_t block_size) {
+// Phase B of both split routes: one thread per block.
+static void launch_event_inserts(const Table& v, const at::Tensor& ehashes,
+                                 const at::Tensor& eh_off,
+                                 const at::Tensor& ev_of,
+                                 const at::Tensor& ev_type,
+                                 const at::Tensor& tok_off,
+                                 const at::Tensor& pod_entry,
+                                 const at::Tensor& model_of,
+                                 int64_t block_size, int64_t epoch,
+                                 int64_t shard_id, int64_t num_shards,
+                                 const at::Tensor& req_scratch) {
+  int64_t n = ehashes.numel();
+  launch_1d(k_event_inserts, n, v, u64p(ehashes), i32p(eh_off), i32p(ev_of),
+            u8p(ev_type), i32p(tok_off), u32p(pod_entry), i32p(model_of), n,
+            (int)block_size, (int32_t)epoch, (int)shard_id, (int)num_shards,
+            u64p(req_scratch));
+}
+
+}  // namespace kvidx
+
+// ---------------------------------------------------------------------
+// Ops: the definitions of what kvidx_ops.h declares.  The names are
+// qualified, so a signature that drifts from its declaration does not
+// compile (it would otherwise be a new overload, and the bound one an
+// undefined symbol at import).
+// ---------------------------------------------------------------------
+
+void kvidx::gpu_insert(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
+                       at::Tensor request_hashes, int64_t model_id,
+                       at::Tensor pod_entries, int64_t epoch, int64_t shard_id,
+                       int64_t num_shards, int64_t emap_write) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  int64_t n = engine_hashes.numel();
+  if (n == 0) return;
+  launch_1d(k_insert, n, v, u64p(engine_hashes), u64p(request_hashes), n,
+            (uint32_t)model_id, u32p(pod_entries), (int)pod_entries.numel(),
+            (int32_t)epoch, (int)shard_id, (int)num_shards, (int)emap_write);
+}
+
+void kvidx::gpu_compact(KVIDX_TABLE_PARAMS, at::Tensor n_keys,
+                        at::Tensor n_meta, at::Tensor n_stamp,
+                        at::Tensor n_pods, at::Tensor n_e_keys,
+                        at::Tensor n_e_meta, at::Tensor n_e_vals) {
+  auto ov = make_table_view(KVIDX_TABLE_ARGS, true);
+  auto nv = make_table_view(n_keys, n_meta, n_stamp, n_pods, n_e_keys,
+                            n_e_meta, n_e_vals, pods_per_key, true);
+  int64_t cap = keys.numel();
+  launch_1d(k_compact_main, cap, ov, nv, cap);
+  launch_1d(k_compact_emap, cap, ov, nv, cap);
+}
+
+void kvidx::gpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
+                      int64_t model_id, at::Tensor pod_entries) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  int64_t n = engine_hashes.numel();
+  if (n == 0) return;
+  launch_1d(k_evict, n, v, u64p(engine_hashes), n, (uint32_t)model_id,
+            u32p(pod_entries), (int)pod_entries.numel());
+}
+
+std::vector<at::Tensor> kvidx::gpu_get_request_keys(
+    KVIDX_TABLE_PARAMS, at::Tensor engine_hashes, int64_t model_id) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  int64_t n = engine_hashes.numel();
+  auto found = at::zeros({n}, engine_hashes.options().dtype(at::kByte));
+  auto out = at::zeros({n}, engine_hashes.options());
+  if (n == 0) return {found, out};
+  launch_1d(k_get_request_keys, n, v, u64p(engine_hashes), n,
+            (uint32_t)model_id, u8p(found), u64p(out));
+  return {found, out};
+}
+
+std::vector<at::Tensor> kvidx::gpu_lookup(KVIDX_TABLE_PARAMS,
+                                          at::Tensor request_hashes,
+                                          int64_t model_id,
+                                          at::Tensor filter_words,
+                                          int64_t num_pods, int64_t epoch,
+                                          int64_t shard_id, int64_t num_shards,
+                                          int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  int64_t K = request_hashes.numel();
+  int64_t W = pod_words(num_pods);
+  n_tiers = clamp_tiers(n_tiers);
+  auto found = at::zeros({K}, request_hashes.options().dtype(at::kByte));
+  // tier planes sized by the registered tier count (see cpu_lookup)
+  auto masks = at::zeros({K, n_tiers, W}, request_hashes.options());
+  if (K == 0) return {found, masks};
+  const uint64_t* filter = filter_ptr(filter_words);
+  launch_1d(k_lookup_masks, K, v, u64p(request_hashes), K, (uint32_t)model_id,
+            filter, filter ? 1 : 0, (int)num_pods, (int)W, (int32_t)epoch,
+            (int)shard_id, (int)num_shards, (int)n_tiers, u8p(found),
+            reinterpret_cast<unsigned long long*>(u64p(masks)));
+  return {found, masks};
+}
+
+at::Tensor kvidx::gpu_fused_score(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                  at::Tensor offsets, int64_t model_id,
+                                  at::Tensor filter_words, at::Tensor weights,
+                                  int64_t num_pods, int64_t epoch,
+                                  int64_t max_k, int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  return launch_fused_score(k_fused_score, v, offsets.numel() - 1, hashes,
+                            model_id, filter_words, weights, num_pods, epoch,
+                            max_k, n_tiers, (const int32_t*)i32p(offsets));
+}
+
+// gpu_fused_score over the padded rows that gpu_hash_chain_tr(row_major=1)
+// returns: hashes int64 [B, stride], n_keys int32 [B] on the device.
+at::Tensor kvidx::gpu_fused_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                       at::Tensor n_keys, int64_t model_id,
+                                       at::Tensor filter_words,
+                                       at::Tensor weights, int64_t num_pods,
+                                       int64_t epoch, int64_t max_k,
+                                       int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  TORCH_CHECK(hashes.is_cuda() && hashes.dtype() == at::kLong &&
+                  hashes.dim() == 2 && hashes.is_contiguous(),
+              "hashes must be a contiguous int64 [B, stride] device tensor");
+  TORCH_CHECK(n_keys.is_cuda() && n_keys.dtype() == at::kInt &&
+                  n_keys.is_contiguous(),
+              "n_keys must be a contiguous int32 device tensor");
+  int64_t B = hashes.size(0);
+  int64_t stride = hashes.size(1);
+  TORCH_CHECK(n_keys.numel() == B, "n_keys must have one entry per row");
+  TORCH_CHECK(max_k <= stride, "max_k exceeds the row length");
+  return launch_fused_score(k_fused_score_rows, v, B, hashes, model_id,
+                            filter_words, weights, num_pods, epoch, max_k,
+                            n_tiers, (const int32_t*)i32p(n_keys), stride);
+}
+
+at::Tensor kvidx::gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
+                                       at::Tensor weights, int64_t num_pods) {
+  int64_t B = offsets.numel() - 1;
+  int64_t W = pod_words(num_pods);
+  TORCH_CHECK(W <= 64, "score_from_masks supports up to 4096 pods");
+  TORCH_CHECK(masks.dim() == 3, "masks must be [Ktot, T, W]");
+  int64_t T = masks.size(1);  // tier planes, sized by the lookup
+  auto scores = at::zeros({B, num_pods}, masks.options().dtype(at::kFloat));
+  if (B == 0) return scores;
+  int wgroups = (int)((W + 15) / 16);
+  hipLaunchKernelGGL(
+      k_score_from_masks, dim3((int)B, wgroups), dim3(64), 0, STREAM,
+      reinterpret_cast<const unsigned long long*>(u64p(masks)),
+      i32p(offsets), weights.data_ptr<float>(), (int)T, (int)num_pods, (int)W,
+      scores.data_ptr<float>());
+  return scores;
+}
+
+std::vector<at::Tensor> kvidx::gpu_hash_chain(
+    at::Tensor tokens, at::Tensor tok_off, at::Tensor parents,
+    int64_t block_size, int64_t algo) {
+  TORCH_CHECK(tokens.is_cuda());
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  int64_t B = parents.numel();
+  auto chunk_off_cpu = at::zeros({B + 1}, at::kLong);
+  {
+    auto off_cpu = tok_off.to(at::kCPU);
+    const int64_t* offp = off_cpu.data_ptr<int64_t>();
+    int64_t* cop = chunk_off_cpu.data_ptr<int64_t>();
+    for (int64_t b = 0; b < B; ++b)
+      cop[b + 1] = cop[b] + (offp[b + 1] - offp[b]) / block_size;
+  }
+  auto chunk_off = chunk_off_cpu.to(tokens.device());
+  int64_t total = chunk_off_cpu.data_ptr<int64_t>()[B];
+  auto out = at::empty({total}, tokens.options());
+  if (B == 0) return {out, chunk_off};
+  dispatch_algo(algo, [&](auto A) {
+    launch_1d(k_hash_chain<decltype(A)::value>, B, tokens.data_ptr<int64_t>(),
+              tok_off.data_ptr<int64_t>(), u64p(parents),
+              chunk_off.data_ptr<int64_t>(), B, (int)block_size, u64p(out));
+  });
+  return {out, chunk_off};
+}
+
+// tokens_t: int32 [T, B] (transposed); parents int64 [B]; n_chunks
+// int32 [B].  Returns out int64 [max_chunks, B] (transposed hashes), or
+// [B, max_chunks] with row_major.  ilp is a retired tuning knob (0 or 1).
+at::Tensor kvidx::gpu_hash_chain_tr(at::Tensor tokens_t, at::Tensor parents,
+                                    at::Tensor n_chunks, int64_t block_size,
+                                    int64_t max_chunks, int64_t ilp,
+                                    int64_t row_major, int64_t algo) {
+  TORCH_CHECK(tokens_t.is_cuda() && tokens_t.dtype() == at::kInt);
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  TORCH_CHECK(ilp == 0 || ilp == 1,
+              "gpu_hash_chain_tr runs one chain per lane: ilp must be 0 or 1 "
+              "(the multi-chain and prefetch variants are gone), got ", ilp);
+  TORCH_CHECK(tokens_t.dim() == 2, "tokens_t must be [T, B]");
+  int64_t B = tokens_t.size(1);
+  TORCH_CHECK(parents.numel() == B && n_chunks.numel() == B);
+  // row_major=1: out is [B, max_chunks] (what the fused-score kernel
+  // consumes directly - no transpose pass); default [max_chunks, B].
+  // Not cleared: the kernels write every slot, a zero where
+  // c >= n_chunks[b].  Keep it so.  A fill kernel in front of the chain
+  // call costs only tens of µs, but with two kernels per call on the
+  // read path's side stream the runtime keeps falling back to running
+  // that stream and the score stream one after the other (call time
+  // 1.2 -> 2.7 ms, flipping between and within processes; measured
+  // with only this line changed, profiles/r04_fnv_chain.md).
+  auto out = at::empty(row_major ? std::initializer_list<int64_t>{B, max_chunks}
+                                 : std::initializer_list<int64_t>{max_chunks, B},
+                       parents.options());
+  if (B == 0 || max_chunks == 0) return out;
+  TORCH_CHECK(tokens_t.size(0) >= max_chunks * block_size,
+              "tokens_t has fewer rows than max_chunks * block_size");
+  auto tokens_c = tokens_t.contiguous();
+  auto launch = [&](auto kern, int threads, size_t lds) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((B + threads - 1) / threads)),
+                       dim3(threads), lds, STREAM, i32p(tokens_c),
+                       u64p(parents), i32p(n_chunks), B, (int)max_chunks,
+                       (int)row_major, u64p(out));
+  };
+  // One prompt per lane either way.  SHA-256: workgroup width set by the
+  // LDS payload columns.  FNV: one-wave workgroups, with row-major output
+  // staged in LDS.  B / 64 waves spread over all CUs before any CU
+  // gets a second one, where 256-thread workgroups put four waves on
+  // each of a quarter as many CUs.  Measured (profiles/r04_fnv_chain.md):
+  // alone, the row-major call is 8 % shorter and the transposed one the
+  // same; beside the score kernel the chain gains what the score kernel
+  // loses, and the chain is the longer stream, so the read call gets
+  // shorter.  A raised wave priority (s_setprio 1 at kernel entry) was
+  // tried with either shape and changed nothing measurable.  Measured
+  // again with row-major output staged through LDS
+  // (profiles/r05_score_walk.md): the two widths give the same call
+  // time, 64 is 0.005..0.008 ms shorter alone; 64 stays.
+  dispatch_algo(algo, [&](auto A) {
+    dispatch_chain_block_size(block_size, [&](auto S) {
+      constexpr int AL = decltype(A)::value;
+      constexpr int BS = decltype(S)::value;
+      if constexpr (AL == ALGO_FNV64A)
+        launch(k_fnv_chain_tr<BS>, 64, row_major ? chain_stage_bytes(64) : 0);
+      else
+        launch(k_sha_chain_tr<BS, AL>, sha_tr_threads(BS), 0);
+    });
+  });
+  return out;
+}
+
+std::vector<at::Tensor> kvidx::gpu_stage_ragged_tokens(
+    at::Tensor tokens, at::Tensor offsets, int64_t block_size) {
   auto p = plan_ragged(tokens, offsets, block_size);
   at::Device dev = tokens.is_cuda()
                        ? tokens.device()
@@ -1561,16 +1366,14 @@ std::vector<at::Tensor> gpu_stage_ragged_tokens(at::Tensor tokens,
 // host wait in between.  Returns float32 [B, num_pods] on the table's
 // device.  Scores equal hash_chain_batch + gpu_fused_score bit for bit:
 // same chain function, same walk.
-at::Tensor gpu_score_flat_tokens(at::Tensor keys, at::Tensor meta,
-                                 at::Tensor stamp, at::Tensor pods,
-                                 at::Tensor e_keys, at::Tensor e_meta,
-                                 at::Tensor e_vals, int64_t pods_per_key,
-                                 at::Tensor tokens_flat, at::Tensor offsets,
-                                 int64_t model_id, at::Tensor filter_words,
-                                 at::Tensor weights, int64_t num_pods,
-                                 int64_t epoch, int64_t init_hash_bits,
-                                 int64_t block_size, int64_t n_tiers,
-                                 int64_t algo) {
+at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
+                                        at::Tensor tokens_flat,
+                                        at::Tensor offsets, int64_t model_id,
+                                        at::Tensor filter_words,
+                                        at::Tensor weights, int64_t num_pods,
+                                        int64_t epoch, int64_t init_hash_bits,
+                                        int64_t block_size, int64_t n_tiers,
+                                        int64_t algo) {
   TORCH_CHECK(keys.is_cuda(), "table must live on the GPU");
   TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
   auto p = plan_ragged(tokens_flat, offsets, block_size);
@@ -1581,14 +1384,10 @@ at::Tensor gpu_score_flat_tokens(at::Tensor keys, at::Tensor meta,
   auto parents = at::full({p.B}, init_hash_bits, fopt.dtype(at::kLong));
   auto hashes = gpu_hash_chain_tr(staged[0], parents, staged[1], block_size,
                                   p.max_k, 0, 1, algo);
-  if (n_tiers < 1) n_tiers = 1;
-  if (n_tiers > MAX_TIERS) n_tiers = MAX_TIERS;
-  int64_t W = (num_pods + 63) / 64;
-  if (W <= 16 && p.max_k * n_tiers * W * 8 <= 64 * 1024)
-    return gpu_fused_score_rows(keys, meta, stamp, pods, e_keys, e_meta,
-                                e_vals, pods_per_key, hashes, staged[1],
-                                model_id, filter_words, weights, num_pods,
-                                epoch, p.max_k, n_tiers);
+  if (fused_score_fits(p.max_k, clamp_tiers(n_tiers), pod_words(num_pods)))
+    return gpu_fused_score_rows(KVIDX_TABLE_ARGS, hashes, staged[1], model_id,
+                                filter_words, weights, num_pods, epoch,
+                                p.max_k, n_tiers);
   // The masks do not fit in LDS (huge fleet x long prompts; rare): gather
   // the live slots of the rows into flat hashes and take the two-kernel
   // path.  The gather index comes from the host's n_chunks, no wait.
@@ -1607,26 +1406,22 @@ at::Tensor gpu_score_flat_tokens(at::Tensor keys, at::Tensor meta,
     op[p.B] = (int32_t)n;
   }
   auto flat = hashes.view({-1}).index_select(0, idx_h.to(dev));
-  auto fm = gpu_lookup(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                       pods_per_key, flat, model_id, filter_words, num_pods,
-                       epoch, 0, 1, n_tiers);
+  auto fm = gpu_lookup(KVIDX_TABLE_ARGS, flat, model_id, filter_words,
+                       num_pods, epoch, 0, 1, n_tiers);
   return gpu_score_from_masks(fm[1].contiguous(), off_h.to(dev), weights,
                               num_pods);
 }
 
-void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
-                      at::Tensor pods, at::Tensor e_keys, at::Tensor e_meta,
-                      at::Tensor e_vals, int64_t pods_per_key,
-                      at::Tensor tokens, at::Tensor tok_off,
-                      at::Tensor ehashes, at::Tensor eh_off,
-                      at::Tensor parents, at::Tensor has_parent,
-                      at::Tensor ev_type, at::Tensor pod_entry,
-                      at::Tensor grp_off, at::Tensor model_of,
-                      int64_t init_hash_bits, int64_t block_size,
-                      int64_t epoch, int64_t shard_id, int64_t num_shards,
-                      int64_t algo) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
+void kvidx::gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,
+                             at::Tensor tok_off, at::Tensor ehashes,
+                             at::Tensor eh_off, at::Tensor parents,
+                             at::Tensor has_parent, at::Tensor ev_type,
+                             at::Tensor pod_entry, at::Tensor grp_off,
+                             at::Tensor model_of, int64_t init_hash_bits,
+                             int64_t block_size, int64_t epoch,
+                             int64_t shard_id, int64_t num_shards,
+                             int64_t algo) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
   int64_t G = grp_off.numel() - 1;
   if (G == 0) return;
   TORCH_CHECK(model_of.numel() == ev_type.numel(),
@@ -1636,17 +1431,13 @@ void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
   const int waves_per_block = 4;
   int blocks = (int)((G + waves_per_block - 1) / waves_per_block);
   dispatch_algo(algo, [&](auto A) {
-  hipLaunchKernelGGL(
-      k_apply_events<decltype(A)::value>, dim3(blocks),
-      dim3(waves_per_block * 64), 0, STREAM, v,
-      tokens.data_ptr<int64_t>(), tok_off.data_ptr<int32_t>(), U64P(ehashes),
-      eh_off.data_ptr<int32_t>(), U64P(parents),
-      has_parent.data_ptr<uint8_t>(), ev_type.data_ptr<uint8_t>(),
-      reinterpret_cast<const uint32_t*>(pod_entry.data_ptr<int32_t>()),
-      grp_off.data_ptr<int32_t>(), model_of.data_ptr<int32_t>(), G,
-      (uint64_t)init_hash_bits, (int)block_size, (int32_t)epoch,
-      (int)shard_id, (int)num_shards,
-      reinterpret_cast<uint64_t*>(req_scratch.data_ptr<int64_t>()));
+    hipLaunchKernelGGL(
+        k_apply_events<decltype(A)::value>, dim3(blocks),
+        dim3(waves_per_block * 64), 0, STREAM, v, tokens.data_ptr<int64_t>(),
+        i32p(tok_off), u64p(ehashes), i32p(eh_off), u64p(parents),
+        u8p(has_parent), u8p(ev_type), u32p(pod_entry), i32p(grp_off),
+        i32p(model_of), G, (uint64_t)init_hash_bits, (int)block_size,
+        (int32_t)epoch, (int)shard_id, (int)num_shards, u64p(req_scratch));
   });
 }
 
@@ -1654,17 +1445,18 @@ void gpu_apply_events(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
 // verified), so chains run one lane per EVENT from transposed int32
 // tokens; inserts thread-per-block as usual.  No bmap is needed -
 // parents resolve via the persistent engine map or the chain root.
-void gpu_apply_events_split_tr(
-    at::Tensor keys, at::Tensor meta, at::Tensor stamp, at::Tensor pods,
-    at::Tensor e_keys, at::Tensor e_meta, at::Tensor e_vals,
-    int64_t pods_per_key, at::Tensor tokens_flat, at::Tensor tok_off,
-    at::Tensor ehashes, at::Tensor eh_off, at::Tensor parents,
-    at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
-    at::Tensor ev_of, at::Tensor model_of, int64_t init_hash_bits,
-    int64_t block_size, int64_t epoch, int64_t shard_id,
-    int64_t num_shards, int64_t max_tokens, int64_t algo) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
+void kvidx::gpu_apply_events_split_tr(KVIDX_TABLE_PARAMS,
+                                      at::Tensor tokens_flat,
+                                      at::Tensor tok_off, at::Tensor ehashes,
+                                      at::Tensor eh_off, at::Tensor parents,
+                                      at::Tensor has_parent,
+                                      at::Tensor ev_type, at::Tensor pod_entry,
+                                      at::Tensor ev_of, at::Tensor model_of,
+                                      int64_t init_hash_bits,
+                                      int64_t block_size, int64_t epoch,
+                                      int64_t shard_id, int64_t num_shards,
+                                      int64_t max_tokens, int64_t algo) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
   TORCH_CHECK(tokens_flat.dtype() == at::kInt,
               "event tokens must be int32 (uint32 bit pattern)");
   TORCH_CHECK(block_size <= 64, "event chain kernel supports block_size<=64");
@@ -1680,52 +1472,33 @@ void gpu_apply_events_split_tr(
     int ygrid = (int)std::min<int64_t>((max_tokens + threads - 1) / threads,
                                        64);
     hipLaunchKernelGGL(k_transpose_ev_tokens, dim3((int)E, ygrid),
-                       dim3(threads), 0, STREAM,
-                       tokens_flat.data_ptr<int32_t>(),
-                       tok_off.data_ptr<int32_t>(), E,
-                       tokens_t.data_ptr<int32_t>());
+                       dim3(threads), 0, STREAM, i32p(tokens_flat),
+                       i32p(tok_off), E, i32p(tokens_t));
   }
   TORCH_CHECK(model_of.numel() == E, "model_of must have one id per event");
   dispatch_algo(algo, [&](auto A) {
-  hipLaunchKernelGGL(k_event_chains_ev<decltype(A)::value>,
-                     dim3((int)((E + threads - 1) / threads)), dim3(threads),
-                     0, STREAM, v, tokens_t.data_ptr<int32_t>(),
-                     tok_off.data_ptr<int32_t>(), U64P(ehashes),
-                     eh_off.data_ptr<int32_t>(), U64P(parents),
-                     has_parent.data_ptr<uint8_t>(),
-                     ev_type.data_ptr<uint8_t>(),
-                     model_of.data_ptr<int32_t>(), E,
-                     (uint64_t)init_hash_bits, (int)block_size,
-                     reinterpret_cast<uint64_t*>(
-                         req_scratch.data_ptr<int64_t>()));
+    launch_1d(k_event_chains_ev<decltype(A)::value>, E, v, i32p(tokens_t),
+              i32p(tok_off), u64p(ehashes), i32p(eh_off), u64p(parents),
+              u8p(has_parent), u8p(ev_type), i32p(model_of), E,
+              (uint64_t)init_hash_bits, (int)block_size, u64p(req_scratch));
   });
-  hipLaunchKernelGGL(k_event_inserts,
-                     dim3((int)((n + threads - 1) / threads)), dim3(threads),
-                     0, STREAM, v, U64P(ehashes), eh_off.data_ptr<int32_t>(),
-                     ev_of.data_ptr<int32_t>(), ev_type.data_ptr<uint8_t>(),
-                     tok_off.data_ptr<int32_t>(),
-                     reinterpret_cast<const uint32_t*>(
-                         pod_entry.data_ptr<int32_t>()),
-                     model_of.data_ptr<int32_t>(), n,
-                     (int)block_size, (int32_t)epoch,
-                     (int)shard_id, (int)num_shards,
-                     reinterpret_cast<uint64_t*>(
-                         req_scratch.data_ptr<int64_t>()));
+  launch_event_inserts(v, ehashes, eh_off, ev_of, ev_type, tok_off, pod_entry,
+                       model_of, block_size, epoch, shard_id, num_shards,
+                       req_scratch);
 }
 
 // Phase-split apply: bmap build -> chains (lane per group) -> inserts
 // (thread per block).  ev_of: int32 [total blocks] = owning event index.
-void gpu_apply_events_split(
-    at::Tensor keys, at::Tensor meta, at::Tensor stamp, at::Tensor pods,
-    at::Tensor e_keys, at::Tensor e_meta, at::Tensor e_vals,
-    int64_t pods_per_key, at::Tensor tokens, at::Tensor tok_off,
-    at::Tensor ehashes, at::Tensor eh_off, at::Tensor parents,
-    at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
-    at::Tensor grp_off, at::Tensor ev_of, at::Tensor model_of,
-    int64_t init_hash_bits, int64_t block_size, int64_t epoch,
-    int64_t shard_id, int64_t num_shards, int64_t algo) {
-  auto v = dev_view(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                    pods_per_key);
+void kvidx::gpu_apply_events_split(KVIDX_TABLE_PARAMS, at::Tensor tokens,
+                                   at::Tensor tok_off, at::Tensor ehashes,
+                                   at::Tensor eh_off, at::Tensor parents,
+                                   at::Tensor has_parent, at::Tensor ev_type,
+                                   at::Tensor pod_entry, at::Tensor grp_off,
+                                   at::Tensor ev_of, at::Tensor model_of,
+                                   int64_t init_hash_bits, int64_t block_size,
+                                   int64_t epoch, int64_t shard_id,
+                                   int64_t num_shards, int64_t algo) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
   int64_t G = grp_off.numel() - 1;
   int64_t n = ehashes.numel();
   if (G == 0 || n == 0) return;
@@ -1734,43 +1507,20 @@ void gpu_apply_events_split(
   auto bkeys = at::zeros({bcap}, ehashes.options());
   auto bvals = at::zeros({bcap}, ehashes.options().dtype(at::kInt));
   auto req_scratch = at::zeros({n}, ehashes.options());
-  int threads = 256;
 
-  hipLaunchKernelGGL(k_batch_bmap,
-                     dim3((int)((n + threads - 1) / threads)), dim3(threads),
-                     0, STREAM, U64P(ehashes), n,
-                     reinterpret_cast<uint64_t*>(bkeys.data_ptr<int64_t>()),
-                     bvals.data_ptr<int32_t>(), bcap - 1);
+  launch_1d(k_batch_bmap, n, u64p(ehashes), n, u64p(bkeys), i32p(bvals),
+            bcap - 1);
   TORCH_CHECK(model_of.numel() == ev_type.numel(),
               "model_of must have one id per event");
   dispatch_algo(algo, [&](auto A) {
-  hipLaunchKernelGGL(k_event_chains<decltype(A)::value>,
-                     dim3((int)((G + threads - 1) / threads)), dim3(threads),
-                     0, STREAM, v, tokens.data_ptr<int64_t>(),
-                     tok_off.data_ptr<int32_t>(), U64P(ehashes),
-                     eh_off.data_ptr<int32_t>(), U64P(parents),
-                     has_parent.data_ptr<uint8_t>(),
-                     ev_type.data_ptr<uint8_t>(), grp_off.data_ptr<int32_t>(),
-                     model_of.data_ptr<int32_t>(),
-                     G, (uint64_t)init_hash_bits,
-                     (int)block_size,
-                     reinterpret_cast<uint64_t*>(bkeys.data_ptr<int64_t>()),
-                     bvals.data_ptr<int32_t>(), bcap - 1,
-                     reinterpret_cast<uint64_t*>(
-                         req_scratch.data_ptr<int64_t>()));
+    launch_1d(k_event_chains<decltype(A)::value>, G, v,
+              tokens.data_ptr<int64_t>(), i32p(tok_off), u64p(ehashes),
+              i32p(eh_off), u64p(parents), u8p(has_parent), u8p(ev_type),
+              i32p(grp_off), i32p(model_of), G, (uint64_t)init_hash_bits,
+              (int)block_size, u64p(bkeys), i32p(bvals), bcap - 1,
+              u64p(req_scratch));
   });
-  hipLaunchKernelGGL(k_event_inserts,
-                     dim3((int)((n + threads - 1) / threads)), dim3(threads),
-                     0, STREAM, v, U64P(ehashes), eh_off.data_ptr<int32_t>(),
-                     ev_of.data_ptr<int32_t>(), ev_type.data_ptr<uint8_t>(),
-                     tok_off.data_ptr<int32_t>(),
-                     reinterpret_cast<const uint32_t*>(
-                         pod_entry.data_ptr<int32_t>()),
-                     model_of.data_ptr<int32_t>(), n,
-                     (int)block_size, (int32_t)epoch,
-                     (int)shard_id, (int)num_shards,
-                     reinterpret_cast<uint64_t*>(
-                         req_scratch.data_ptr<int64_t>()));
+  launch_event_inserts(v, ehashes, eh_off, ev_of, ev_type, tok_off, pod_entry,
+                       model_of, block_size, epoch, shard_id, num_shards,
+                       req_scratch);
 }
-
-}  // namespace kvidx

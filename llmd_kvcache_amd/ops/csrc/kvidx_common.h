@@ -193,12 +193,12 @@ KVIDX_HD uint64_t fnv_cbor_u64_wide(uint64_t h, uint64_t v) {
 // The token loop is force-unrolled on device: a rolled loop makes hipcc
 // read tok[] via gpr_idx (register-indexed) with a vmcnt(0) wait at the
 // loop head, which both serializes the reads and drains any prefetched
-// next-chunk loads (measured in the k_hash_chain_tr ISA).
+// next-chunk loads (measured in the FNV chain kernel's ISA).
 //
 // wide_parent: the caller promises parent > 0xFFFFFFFF, which a chained
 // parent (a 64-bit hash) is with probability 1 - 2^-32; the parent item
 // is then nine straight steps in place of eight predicated ones.  On the
-// device the flag must be uniform over the wave (k_hash_chain_tr votes
+// device the flag must be uniform over the wave (k_fnv_chain_tr votes
 // on it) so that taking it is a scalar branch.  Callers that run one
 // chain on a single lane or per-lane event chains (the ingest kernels)
 // pass false: they have no whole wave to vote with, and a per-lane
@@ -254,7 +254,7 @@ KVIDX_HD uint64_t chunk_hash(uint64_t parent, const TokT* tokens, int n) {
 //    caller-provided word buffer first (an LDS column on the GPU), then
 //    runs the compression for the wave-maximum block count with a
 //    per-lane select - every lane compresses at the same time, so the 64
-//    rounds never diverge (the read-path kernel k_hash_chain_tr).
+//    rounds never diverge (the read-path kernel k_sha_chain_tr).
 // ---------------------------------------------------------------------
 
 static constexpr int ALGO_FNV64A = 0;
@@ -547,6 +547,46 @@ KVIDX_HD uint32_t pod_entry_tier(uint32_t e) { return (e >> 24) & 0xFu; }
 // Probe start position (golden-ratio scramble so clustered hashes spread).
 KVIDX_HD uint64_t probe_start(uint64_t h, uint64_t cap_mask) {
   return (h * 0x9E3779B97F4A7C15ull) & cap_mask;
+}
+
+// Raw view of one table bundle (layout above); the arrays never alias.
+struct Table {
+  uint64_t* __restrict__ keys;
+  uint32_t* __restrict__ meta;
+  int32_t* __restrict__ stamp;
+  uint32_t* __restrict__ pods;
+  uint64_t* __restrict__ e_keys;
+  uint32_t* __restrict__ e_meta;
+  uint64_t* __restrict__ e_vals;
+  uint64_t cap_mask;
+  int pods_per_key;
+};
+
+// Slot of the live (occupied, not tombstoned) entry for (h, model) in a
+// keys/meta pair - the main table or the engine map - or -1.  A never-used
+// key word ends the probe chain.
+KVIDX_HD int64_t probe_find(const uint64_t* __restrict__ keys,
+                            const uint32_t* __restrict__ meta,
+                            uint64_t cap_mask, uint64_t h, uint32_t model) {
+  h = remap_hash(h);
+  uint64_t s = probe_start(h, cap_mask);
+  for (int t = 0; t < PROBE_MAX; ++t) {
+    uint64_t i = (s + t) & cap_mask;
+    uint64_t k = keys[i];
+    if (k == 0) return -1;
+    uint32_t m = meta[i];
+    if ((m & META_OCC) && !(m & META_TOMB) && k == h &&
+        (m & META_MODEL_MASK) == model)
+      return (int64_t)i;
+  }
+  return -1;
+}
+
+// Sharding: the main table holds only the keys a shard owns (the engine
+// map is replicated on every shard).
+KVIDX_HD bool owns_key(uint64_t h, int shard_id, int num_shards) {
+  return num_shards <= 1 ||
+         (int)(remap_hash(h) % (uint64_t)num_shards) == shard_id;
 }
 
 }  // namespace kvidx

@@ -52,35 +52,9 @@
 #include <thread>
 #include <vector>
 
-#include <torch/extension.h>
+#include "kvidx_ops.h"
 
 namespace kvidx {
-
-// cpu_ops.cpp / hip_ops.hip (same extension)
-std::vector<at::Tensor> hash_chain_batch(at::Tensor, at::Tensor, at::Tensor,
-                                         int64_t, int64_t);
-at::Tensor cpu_fused_score(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                           at::Tensor, at::Tensor, at::Tensor, int64_t,
-                           at::Tensor, at::Tensor, int64_t, at::Tensor,
-                           at::Tensor, int64_t, int64_t);
-#ifdef KVIDX_WITH_HIP
-at::Tensor gpu_fused_score(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                           at::Tensor, at::Tensor, at::Tensor, int64_t,
-                           at::Tensor, at::Tensor, int64_t, at::Tensor,
-                           at::Tensor, int64_t, int64_t, int64_t, int64_t);
-std::vector<at::Tensor> gpu_lookup(at::Tensor, at::Tensor, at::Tensor,
-                                   at::Tensor, at::Tensor, at::Tensor,
-                                   at::Tensor, int64_t, at::Tensor, int64_t,
-                                   at::Tensor, int64_t, int64_t, int64_t,
-                                   int64_t, int64_t);
-at::Tensor gpu_score_from_masks(at::Tensor, at::Tensor, at::Tensor, int64_t);
-at::Tensor gpu_score_flat_tokens(at::Tensor, at::Tensor, at::Tensor,
-                                 at::Tensor, at::Tensor, at::Tensor,
-                                 at::Tensor, int64_t, at::Tensor, at::Tensor,
-                                 int64_t, at::Tensor, at::Tensor, int64_t,
-                                 int64_t, int64_t, int64_t, int64_t, int64_t);
-#endif
-
 namespace wire {
 
 namespace py = pybind11;

@@ -1,16 +1,18 @@
-"""Hash-chain kernel sweep on MI355X: batch x ILP grid.
+"""Hash-chain kernel sweep on MI355X: batch x algo grid.
 
     python scripts/sweep_chain.py
     python scripts/sweep_chain.py --algo fnv-64a,sha256-cbor-64 \
-        --batches 512,4096,32768 --ilp 1 --repeats 5
+        --batches 512,4096,32768 --repeats 5
+    python scripts/sweep_chain.py --block-size 32 --row-major
 
 --algo takes one or more hash_algo names (utils.hashing.NATIVE_ALGO_IDS);
 with several, each batch size is measured for every algo back to back in
-the same process, so the rows are directly comparable.  ILP is an FNV
-tuning knob: the SHA-256 kernel always runs one chain per lane and is
-measured once per batch.  Every cell is warmed up, then timed `--repeats`
-times over `--iters` launches each (host clock around a device
-synchronise); min / median / max of the repeats are printed.
+the same process, so the rows are directly comparable.  --row-major
+measures the [B, max_chunks] output the read path consumes (the FNV
+kernel stages it through LDS) instead of the transposed default.  Every
+cell is warmed up, then timed `--repeats` times over `--iters` launches
+each (host clock around a device synchronise); min / median / max of the
+repeats are printed.
 """
 import argparse
 import statistics
@@ -35,11 +37,11 @@ def main():
                          f"({', '.join(hashing.NATIVE_ALGO_IDS)})")
     ap.add_argument("--batches", type=_ints,
                     default=(512, 1024, 2048, 4096, 8192, 16384))
-    ap.add_argument("--ilp", type=_ints, default=(1, 9, 2, 4),
-                    help="FNV ILP variants to try (SHA ignores it)")
     ap.add_argument("--chunks", type=int, default=512,
                     help="chunks per prompt (8k tokens / bs 16)")
     ap.add_argument("--block-size", type=int, default=16)
+    ap.add_argument("--row-major", action="store_true",
+                    help="write [B, max_chunks] instead of [max_chunks, B]")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=1)
     args = ap.parse_args()
@@ -51,7 +53,8 @@ def main():
     mod = cpu_ext.require()
     K = args.chunks
     BS = args.block_size
-    results = []
+    row_major = int(args.row_major)
+    layout = "row-major" if row_major else "transposed"
     for B in args.batches:
         toks = torch.randint(0, 1 << 31, (K * BS, B), dtype=torch.int32,
                              device="cuda")
@@ -62,37 +65,26 @@ def main():
             parents = torch.full(
                 (B,), init - (1 << 64) if init >= (1 << 63) else init,
                 dtype=torch.int64, device="cuda")
-            for ilp in (args.ilp if algo_id == 0 else (1,)):
-                if B // ilp < 64:
-                    continue
 
-                def call():
-                    return mod.gpu_hash_chain_tr(toks, parents, nch, BS, K,
-                                                 ilp, 0, algo_id)
+            def call():
+                return mod.gpu_hash_chain_tr(toks, parents, nch, BS, K, 0,
+                                             row_major, algo_id)
 
-                call()  # warmup
+            call()  # warmup
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(args.repeats):
+                t0 = time.monotonic()
+                for _ in range(args.iters):
+                    call()
                 torch.cuda.synchronize()
-                times = []
-                for _ in range(args.repeats):
-                    t0 = time.monotonic()
-                    for _ in range(args.iters):
-                        call()
-                    torch.cuda.synchronize()
-                    times.append((time.monotonic() - t0) / args.iters)
-                dt = statistics.median(times)
-                results.append((B, algo, ilp, dt * 1e3, B / dt))
-                print(f"B={B:6d} algo={algo} ilp={ilp} {dt*1e3:8.3f} ms "
-                      f"(min {min(times)*1e3:.3f} max {max(times)*1e3:.3f}, "
-                      f"n={len(times)})  "
-                      f"{B/dt/1e6:8.3f} M prompts/s  "
-                      f"{B*K/dt/1e9:6.2f} G chunks/s", flush=True)
-    best = {}
-    for B, algo, ilp, ms, qps in results:
-        k = (B, algo)
-        if k not in best or qps > best[k][1]:
-            best[k] = (ilp, qps)
-    print("best ILP per (batch, algo):",
-          {k: v[0] for k, v in sorted(best.items())})
+                times.append((time.monotonic() - t0) / args.iters)
+            dt = statistics.median(times)
+            print(f"B={B:6d} bs={BS} {layout} algo={algo} {dt*1e3:8.3f} ms "
+                  f"(min {min(times)*1e3:.3f} max {max(times)*1e3:.3f}, "
+                  f"n={len(times)})  "
+                  f"{B/dt/1e6:8.3f} M prompts/s  "
+                  f"{B*K/dt/1e9:6.2f} G chunks/s", flush=True)
 
 
 if __name__ == "__main__":

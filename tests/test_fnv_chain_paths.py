@@ -172,13 +172,20 @@ def test_ragged_lengths_and_zero_slots_sha(ops, B, row_major):
 
 
 @pytest.mark.parametrize("bs,ilp", [(4, 0), (8, 0), (32, 0), (64, 0),
-                                    (16, 0), (16, 1), (16, 2), (16, 4),
-                                    (16, 8)])
+                                    (16, 0), (16, 1)])
 def test_other_instantiations(ops, bs, ilp):
-    """Every FNV kernel the op can launch: the ILP bodies at the other
-    block sizes and, at 16, each value of the ilp argument (8 is the
-    prefetch variant)."""
+    """Every FNV kernel the op can launch: each block size, and at 16 both
+    values the retired ilp argument still accepts."""
     prompts, parents = _ragged(random.Random(bs * 10 + ilp), 257, bs)
     for row_major in (0, 1):
         _check(ops, FNV, prompts, parents, bs, 5, ilp=ilp,
                row_major=row_major)
+
+
+def test_ilp_above_one_is_rejected(ops):
+    """ilp is no selector any more: one chain per lane is the only kernel."""
+    tt = _tokens_t([[1] * 16], 16)
+    par = torch.zeros(1, dtype=torch.int64, device="cuda")
+    nch = torch.ones(1, dtype=torch.int32, device="cuda")
+    with pytest.raises(RuntimeError, match="ilp must be 0 or 1"):
+        ops.gpu_hash_chain_tr(tt, par, nch, 16, 1, 2, 0, 0)
