@@ -44,6 +44,10 @@ container-smoke:
 
 .PHONY: asan
 asan:
+	mkdir -p build
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=all -o build/asan_check scripts/asan_check.cc \
 	    && ./build/asan_check
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	    -fno-sanitize-recover=all -o build/purge_asan_check \
+	    scripts/purge_asan_check.cc && ./build/purge_asan_check

@@ -154,3 +154,22 @@ def index_config_from_dict(data: Dict[str, Any]) -> IndexConfig:
 
 def config_from_json(blob: str, base: Optional[Config] = None) -> Config:
     return config_from_dict(json.loads(blob), base)
+
+
+def events_config_from_dict(data: Dict[str, Any], base=None):
+    """Overlay for the write path's EventsConfig - the "kv_events" object
+    of a service config file (zmq_endpoint, topic_filter, concurrency,
+    clear_on_all_blocks_cleared).  Unknown keys are ignored, absent keys
+    keep their defaults."""
+    from .kvevents.pool import EventsConfig
+
+    return _apply(base or EventsConfig(), data or {})
+
+
+def events_config_from_json(blob: str, base=None):
+    """Accepts either the whole service config (its "kv_events" object is
+    used, defaults when absent) or a bare EventsConfig object."""
+    data = json.loads(blob)
+    if isinstance(data, dict) and "kv_events" in data:
+        data = data["kv_events"]
+    return events_config_from_dict(data, base)

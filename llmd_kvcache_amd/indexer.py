@@ -134,6 +134,24 @@ class Indexer:
     def kv_block_index(self) -> Index:
         return self._kv_block_index
 
+    # -- pod lifecycle (an extra: the reference never forgets a pod) ----
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> Dict[str, object]:
+        """Drop every block these pods are listed for (one model, or
+        all); the pods stay known.  Returns {"entries_cleared",
+        "keys_tombstoned", "pods"}.  Raises NotImplementedError on
+        backends that cannot purge by pod (Redis/Valkey)."""
+        return self._kv_block_index.clear_pods(list(pods), model_name)
+
+    def remove_pods(self, pods: Sequence[str]) -> Dict[str, object]:
+        """Retire pods that are gone for good (a rollout replaced them):
+        their blocks are dropped and, on table-backed indexes, their ids
+        return to the registry, so the pod-word width of the read path
+        shrinks again.  The caller guarantees that no more events for
+        these pods are in flight; a late event only re-interns the name
+        under a fresh id."""
+        return self._kv_block_index.retire_pods(list(pods))
+
     def get_pod_scores(
         self,
         render_req,

@@ -161,6 +161,39 @@ class CostAwareMemoryIndex(Index):
         with self._mu:
             return self._engine_to_request.get(engine_key)
 
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        """Strip these pods from every key under the global lock; a key
+        that becomes empty leaves with its cost, as in evict (its engine
+        mappings go with it, as budget eviction does)."""
+        wanted = set(pods)
+        seen: Set[str] = set()
+        entries_cleared = keys_dropped = 0
+        with self._mu:
+            for key in list(self._data.keys()) if wanted else ():
+                if model_name is not None and key.model_name != model_name:
+                    continue
+                entries = self._data[key]
+                doomed = [e for e in entries if e.pod_identifier in wanted]
+                if not doomed:
+                    continue
+                for e in doomed:
+                    del entries[e]
+                    seen.add(e.pod_identifier)
+                entries_cleared += len(doomed)
+                if not entries:
+                    del self._data[key]
+                    self._total_cost -= self._costs.pop(key, 0)
+                    self._unmap_request(key)
+                    keys_dropped += 1
+                else:
+                    self._set_cost(key, entries)
+        return {"entries_cleared": entries_cleared,
+                "keys_tombstoned": keys_dropped, "pods": sorted(seen)}
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        return self.clear_pods(pods, None)
+
     @property
     def total_cost_bytes(self) -> int:
         with self._mu:

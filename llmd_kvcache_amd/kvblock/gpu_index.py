@@ -19,6 +19,7 @@ ids (Registry); the table stores only ids.
 
 from __future__ import annotations
 
+import heapq
 import threading
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Set, Tuple
@@ -46,12 +47,19 @@ def _to_u64(v: int) -> int:
 
 
 class Registry:
-    """Interns pod/model/tier strings to dense ids (thread-safe)."""
+    """Interns pod/model/tier strings to dense ids (thread-safe).
+
+    Pod ids can be given back (``release_pods``): a released id holds the
+    empty string in ``id_to_pod`` and is absent from ``pod_to_id``.
+    ``pod_id`` reuses the LOWEST free id before growing - a deterministic
+    policy, so replicated ranks fed the same stream agree - and trailing
+    free ids are trimmed, so ``num_pods`` shrinks again."""
 
     def __init__(self, tier_names: Optional[Sequence[str]] = None):
         self._lock = threading.Lock()
         self.pod_to_id: Dict[str, int] = {}
         self.id_to_pod: List[str] = []
+        self._free_pod_ids: List[int] = []  # min-heap of holes in id_to_pod
         self.model_to_id: Dict[str, int] = {}
         self.id_to_model: List[str] = []
         tiers = list(tier_names or [b.name for b in default_kv_cache_backend_configs()])
@@ -77,15 +85,57 @@ class Registry:
         return tid
 
     def pod_id(self, pod: str) -> int:
+        if not pod:
+            raise ValueError("pod identifier must not be empty")
         with self._lock:
             pid = self.pod_to_id.get(pod)
             if pid is None:
-                if len(self.id_to_pod) >= MAX_PODS:
-                    raise ValueError(f"pod registry full ({MAX_PODS})")
-                pid = len(self.id_to_pod)
+                if self._free_pod_ids:
+                    pid = heapq.heappop(self._free_pod_ids)
+                    self.id_to_pod[pid] = pod
+                else:
+                    if len(self.id_to_pod) >= MAX_PODS:
+                        raise ValueError(f"pod registry full ({MAX_PODS})")
+                    pid = len(self.id_to_pod)
+                    self.id_to_pod.append(pod)
                 self.pod_to_id[pod] = pid
-                self.id_to_pod.append(pod)
             return pid
+
+    def release_pods(self, pods: Sequence[str]) -> List[int]:
+        """Give back the ids of these pods (unknown names are ignored);
+        returns the released ids.  The caller has already purged them
+        from every table that shares this registry."""
+        with self._lock:
+            released = []
+            for pod in pods:
+                pid = self.pod_to_id.pop(pod, None)
+                if pid is None:
+                    continue
+                self.id_to_pod[pid] = ""
+                heapq.heappush(self._free_pod_ids, pid)
+                released.append(pid)
+            if released:
+                self._trim_free_tail()
+            return released
+
+    def _trim_free_tail(self) -> None:
+        n = len(self.id_to_pod)
+        while n and not self.id_to_pod[n - 1]:
+            n -= 1
+        if n != len(self.id_to_pod):
+            del self.id_to_pod[n:]
+            self._free_pod_ids = [i for i in self._free_pod_ids if i < n]
+            heapq.heapify(self._free_pod_ids)
+
+    def _set_pods(self, names: Sequence[str]) -> None:
+        """Replace the pod id space (checkpoint load); empty names are
+        free ids.  Caller holds the lock."""
+        self.id_to_pod = list(names)
+        self.pod_to_id = {p: i for i, p in enumerate(self.id_to_pod) if p}
+        self._free_pod_ids = [i for i, p in enumerate(self.id_to_pod)
+                              if not p]
+        heapq.heapify(self._free_pod_ids)
+        self._trim_free_tail()
 
     def model_id(self, model: str) -> int:
         with self._lock:
@@ -188,6 +238,18 @@ class KvTable:
     def evict(self, engine_hashes, model_id, pod_entries):
         fn = self.ops.gpu_evict if self.is_cuda else self.ops.cpu_evict
         fn(*self._t(), engine_hashes, model_id, pod_entries)
+
+    def purge_pods(self, purge_words, model_id: int = -1) -> Tuple[int, int]:
+        """Strip a set of pods from every pod set of the table (model_id
+        -1: of every model) and tombstone the keys that become empty.
+        purge_words: int64 [W], bit pid % 64 of word pid // 64 selects
+        pod id pid.  Returns (entries_cleared, keys_tombstoned); on a GPU
+        table the sweep has completed when this returns."""
+        words = purge_words.to(device=self.device, dtype=torch.int64)
+        fn = (self.ops.gpu_purge_pods if self.is_cuda
+              else self.ops.cpu_purge_pods)
+        entries, keys = fn(*self._t(), words.contiguous(), model_id)
+        return int(entries), int(keys)
 
     def lookup(self, request_hashes, model_id, filter_words, num_pods,
                sharded=True, n_tiers=MAX_TIERS):
@@ -324,6 +386,7 @@ class TableIndex(Index):
         masks_l = masks.cpu().tolist()  # one bulk D2H/convert, no per-item
         W = masks.shape[2]
         n_tiers = masks.shape[1]
+        pod_names = list(self.registry.id_to_pod)  # "" = released id
 
         result: Dict[Key, List[PodEntry]] = {}
         for i, key in enumerate(request_keys):
@@ -344,9 +407,9 @@ class TableIndex(Index):
                         b = (bits & -bits).bit_length() - 1
                         bits &= bits - 1
                         pid = w * 64 + b
-                        if pid < len(self.registry.id_to_pod):
+                        if pid < len(pod_names) and pod_names[pid]:
                             entries.append(PodEntry(
-                                self.registry.id_to_pod[pid], tier_name))
+                                pod_names[pid], tier_name))
             if entries:
                 result[key] = entries
         return result
@@ -380,6 +443,56 @@ class TableIndex(Index):
         if int(found[0]) == 0:
             return None
         return Key(engine_key.model_name, _to_u64(int(out[0])))
+
+    # -- purge by pod --------------------------------------------------
+    def _purge_locked(self, pods: Sequence[str],
+                      model_name: Optional[str]) -> dict:
+        """clear_pods body; the caller holds _write_lock."""
+        reg = self.registry
+        known = sorted({p for p in pods if p in reg.pod_to_id})
+        out = {"entries_cleared": 0, "keys_tombstoned": 0, "pods": known}
+        model_id = -1
+        if model_name is not None:
+            model_id = reg.model_to_id.get(model_name)
+            if model_id is None:
+                return out  # a model nobody stored under: nothing to clear
+        ids = [reg.pod_to_id[p] for p in known]
+        if not ids:
+            return out  # empty effective set: no launch
+        words = [0] * (max(ids) // 64 + 1)
+        for pid in ids:
+            words[pid // 64] |= 1 << (pid % 64)
+        purge_words = torch.tensor([_to_i64(w) for w in words],
+                                   dtype=torch.int64)
+        entries, keys = self.table.purge_pods(purge_words, model_id)
+        out["entries_cleared"] = entries
+        out["keys_tombstoned"] = keys
+        return out
+
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        """Remove every entry of these pods (of one model, or of all) and
+        tombstone the keys that become empty.  The pods keep their ids:
+        they are alive and will report blocks again.  Unknown pod names
+        are ignored.  One sweep over the table, on its device."""
+        with self._write_lock:
+            return self._purge_locked(pods, model_name)
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        """clear_pods for all models, then give the pods' ids back to the
+        registry (lowest-free reuse, trailing ids trimmed - the score
+        width W shrinks again).
+
+        The ids are released only after the sweep has completed on the
+        device, and still under the write lock, so no entry of a released
+        id is left for the id's next owner to inherit.  Caller contract:
+        no more events for a retired pod are in flight.  A late event is
+        not an error - it re-interns the name under a fresh id - but what
+        it stores stays until the pod is retired again."""
+        with self._write_lock:
+            out = self._purge_locked(pods, None)
+            self.registry.release_pods(out["pods"])
+            return out
 
     # -- fast paths ----------------------------------------------------
     def fused_scores(self, hashes: torch.Tensor, counts_or_offsets: torch.Tensor,
@@ -449,8 +562,7 @@ class TableIndex(Index):
         self.table.load_state_dict(state)
         r = self.registry
         with r._lock:
-            r.id_to_pod = list(reg["pods"])
-            r.pod_to_id = {p: i for i, p in enumerate(r.id_to_pod)}
+            r._set_pods(reg["pods"])  # "" entries rebuild the free list
             r.id_to_model = list(reg["models"])
             r.model_to_id = {m: i for i, m in enumerate(r.id_to_model)}
             r.id_to_tier = list(reg["tiers"])
@@ -470,10 +582,10 @@ class TableIndex(Index):
         vals = sc[nzi[:, 0], nzi[:, 1]].tolist()
         rows = nzi[:, 0].tolist()
         cols = nzi[:, 1].tolist()
-        names = self.registry.id_to_pod
+        names = list(self.registry.id_to_pod)  # "" = released id
         n_names = len(names)
         for r, c, v in zip(rows, cols, vals):
-            if c < n_names:
+            if c < n_names and names[c]:
                 out[r][names[c]] = v
         return out
 
@@ -570,13 +682,51 @@ class GpuIndex(TableIndex):
             raise RuntimeError("GpuIndexConfig.device must be a cuda device")
 
     def apply_event_batches(self, batches: List[Tuple[str, str, list]],
-                            token_processor=None) -> None:
+                            token_processor=None,
+                            clear_on_all_blocks_cleared: bool = False) -> None:
         """Apply decoded KV event batches fully on-device.
 
         batches: list of (pod_identifier, model_name, [events]) in arrival
         order; per-pod ordering is preserved by grouping (one wave per pod
         group processes its events serially - kvevents/pool.go:132-144).
+
+        clear_on_all_blocks_cleared: an AllBlocksCleared event purges its
+        pod's entries for that model at the event's position: what the
+        burst holds up to there is applied, the pod is swept
+        (k_purge_pods, same stream), and the rest of the burst follows.
+        The pod keeps its id.  A burst without such an event, or with the
+        option off, takes the one-pass path unchanged.
         """
+        from ..kvevents.events import AllBlocksCleared
+
+        # named through the class: callers bind this method to plain
+        # TableIndex objects (the sharded service's local shard)
+        apply = GpuIndex._apply_event_batches
+        if clear_on_all_blocks_cleared and any(
+                isinstance(ev, AllBlocksCleared)
+                for _, _, events in batches for ev in events):
+            pending: List[Tuple[str, str, list]] = []
+            for pod, model, events in batches:
+                start = 0
+                for i, ev in enumerate(events):
+                    if not isinstance(ev, AllBlocksCleared):
+                        continue
+                    if i > start:
+                        pending.append((pod, model, events[start:i]))
+                    if pending:
+                        apply(self, pending, token_processor)
+                        pending = []
+                    self.clear_pods([pod], model)
+                    start = i + 1
+                if start < len(events):
+                    pending.append((pod, model, events[start:]))
+            if pending:
+                apply(self, pending, token_processor)
+            return
+        apply(self, batches, token_processor)
+
+    def _apply_event_batches(self, batches: List[Tuple[str, str, list]],
+                             token_processor=None) -> None:
         from ..kvevents.events import (AllBlocksCleared, BlockRemoved,
                                        BlockStored, get_hash_as_uint64)
 

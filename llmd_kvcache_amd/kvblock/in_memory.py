@@ -130,3 +130,42 @@ class InMemoryIndex(Index):
     def get_request_key(self, engine_key: Key) -> Optional[Key]:
         request_key, found = self._engine_to_request.get(engine_key)
         return request_key if found else None
+
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        """Walk the key LRU (a snapshot of it; recency is left alone) and
+        strip these pods from every pod cache, dropping keys that become
+        empty as evict does.  Engine-key mappings stay: they age out of
+        their own LRU, and the table backends keep theirs too."""
+        wanted = set(pods)
+        seen: Set[str] = set()
+        entries_cleared = keys_dropped = 0
+        if wanted:
+            for key in self._data.keys():
+                if model_name is not None and key.model_name != model_name:
+                    continue
+                pod_cache, found = self._data.peek(key)
+                if not found or pod_cache is None:
+                    continue
+                with pod_cache.mu:
+                    doomed = [e for e in pod_cache.cache.keys()
+                              if e.pod_identifier in wanted]
+                    for e in doomed:
+                        pod_cache.cache.remove(e)
+                        seen.add(e.pod_identifier)
+                    is_empty = len(pod_cache.cache) == 0
+                entries_cleared += len(doomed)
+                if doomed and is_empty:
+                    current, still_exists = self._data.peek(key)
+                    if still_exists and current is not None:
+                        with current.mu:
+                            still_empty = len(current.cache) == 0
+                        if still_empty and self._data.remove(key):
+                            keys_dropped += 1
+        return {"entries_cleared": entries_cleared,
+                "keys_tombstoned": keys_dropped, "pods": sorted(seen)}
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        """No id space to give back here: the same as clear_pods for all
+        models."""
+        return self.clear_pods(pods, None)

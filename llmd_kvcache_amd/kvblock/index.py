@@ -44,6 +44,24 @@ class Index:
         (the Go version returns an error; callers only check presence)."""
         raise NotImplementedError
 
+    # -- purge by pod (an extra: the reference has no counterpart) ------
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        """Remove every entry of these pods (of one model, or of all when
+        model_name is None) and drop the keys that become empty.  Returns
+        {"entries_cleared", "keys_tombstoned", "pods"}; "pods" lists the
+        names the backend acted on.  Backends that cannot do this raise
+        NotImplementedError."""
+        raise NotImplementedError(
+            f"{type(self).__name__} cannot purge by pod")
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        """clear_pods for all models, then forget the pods themselves
+        (table-backed indexes give their pod ids back).  Caller contract:
+        no more events for a retired pod are in flight."""
+        raise NotImplementedError(
+            f"{type(self).__name__} cannot purge by pod")
+
 
 @dataclass
 class IndexConfig:

@@ -112,5 +112,17 @@ class InstrumentedIndex(Index):
     def get_request_key(self, engine_key: Key) -> Optional[Key]:
         return self.inner.get_request_key(engine_key)
 
+    def _count_purge(self, out: dict) -> dict:
+        if collector.evictions is not None:
+            collector.evictions.inc(out.get("keys_tombstoned", 0))
+        return out
+
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        return self._count_purge(self.inner.clear_pods(pods, model_name))
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        return self._count_purge(self.inner.retire_pods(pods))
+
     def __getattr__(self, name):
         return getattr(self.inner, name)

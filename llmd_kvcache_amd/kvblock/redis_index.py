@@ -208,6 +208,22 @@ class RedisIndex(Index):
         except ValueError:
             return None
 
+    # Purge by pod would be a SCAN over the whole keyspace of a server
+    # that other indexers and other applications share, with an HDEL per
+    # hit: minutes of load on someone else's server, started by one HTTP
+    # call.  That decision is the operator's (a maintenance script against
+    # the server), not this backend's.
+    _PURGE_MSG = ("purge by pod is not implemented for the Redis/Valkey "
+                  "backend: it needs a full-keyspace scan of a shared "
+                  "server, which is left to the operator")
+
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        raise NotImplementedError(self._PURGE_MSG)
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        raise NotImplementedError(self._PURGE_MSG)
+
 
 class ValkeyIndex(RedisIndex):
     backend_name = "valkey"

@@ -103,6 +103,45 @@ class TieredIndex(Index):
             rk = self.cold.get_request_key(engine_key)
         return rk
 
+    # -- purge by pod --------------------------------------------------
+    @staticmethod
+    def _merge_purge(outs) -> dict:
+        return {
+            "entries_cleared": sum(o["entries_cleared"] for o in outs),
+            "keys_tombstoned": sum(o["keys_tombstoned"] for o in outs),
+            "pods": sorted({p for o in outs for p in o["pods"]}),
+        }
+
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> dict:
+        """Both tiers are swept: a pod left in the cold tier would be
+        promoted straight back into the hot one."""
+        return self._merge_purge([self.hot.clear_pods(pods, model_name),
+                                  self.cold.clear_pods(pods, model_name)])
+
+    def retire_pods(self, pods: Sequence[str]) -> dict:
+        """Purge both tiers, then release the ids ONCE: the tiers share
+        one registry, so the second tier must still know the names when
+        its sweep runs.  With table tiers both write locks are held from
+        the first sweep to the release."""
+        from .gpu_index import TableIndex
+
+        shared = getattr(self.cold, "registry", None) is self.registry
+        if (shared and isinstance(self.hot, TableIndex)
+                and isinstance(self.cold, TableIndex)):
+            with self.hot._write_lock, self.cold._write_lock:
+                out = self._merge_purge(
+                    [self.hot._purge_locked(pods, None),
+                     self.cold._purge_locked(pods, None)])
+                self.registry.release_pods(out["pods"])
+                return out
+        if not shared:  # separate id spaces: each tier retires its own
+            return self._merge_purge([self.hot.retire_pods(pods),
+                                      self.cold.retire_pods(pods)])
+        out = self.clear_pods(pods, None)
+        self.registry.release_pods(out["pods"])
+        return out
+
     # -- fast paths ----------------------------------------------------
     @property
     def table(self):  # events-pool burst path detection
@@ -112,8 +151,13 @@ class TieredIndex(Index):
     def device(self):
         return self.hot.device
 
-    def apply_event_batches(self, batches, token_processor=None) -> None:
-        self.hot.apply_event_batches(batches, token_processor)
+    def apply_event_batches(self, batches, token_processor=None,
+                            clear_on_all_blocks_cleared: bool = False) -> None:
+        if clear_on_all_blocks_cleared:
+            self.hot.apply_event_batches(batches, token_processor,
+                                         clear_on_all_blocks_cleared=True)
+        else:
+            self.hot.apply_event_batches(batches, token_processor)
         # mirror into the capacity tier through the CPU digest path
         from ..kvevents.pool import digest_events
 
@@ -122,7 +166,9 @@ class TieredIndex(Index):
 
             token_processor = ChunkedTokenDatabase()
         for pod, model, events in batches:
-            digest_events(self.cold, token_processor, pod, model, events)
+            digest_events(
+                self.cold, token_processor, pod, model, events,
+                clear_on_all_blocks_cleared=clear_on_all_blocks_cleared)
 
     def fused_scores(self, hashes, counts_or_offsets, model_name,
                      pod_identifier_set, weights=None, max_k=None):

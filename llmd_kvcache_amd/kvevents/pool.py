@@ -50,6 +50,10 @@ class EventsConfig:
     zmq_endpoint: str = DEFAULT_ZMQ_ENDPOINT
     topic_filter: str = DEFAULT_TOPIC_FILTER
     concurrency: int = DEFAULT_CONCURRENCY
+    # AllBlocksCleared (vLLM sends it on reset_prefix_cache) purges the
+    # pod's entries for that model.  Off by default: the reference
+    # treats the event as a no-op.
+    clear_on_all_blocks_cleared: bool = False
 
 
 @dataclass
@@ -179,7 +183,12 @@ class EventsPool:
         # mixed-model bursts apply in ONE launch: the kernels take a
         # per-event model id (model_of), so no host-side model split
         try:
-            self.index.apply_event_batches(batches, self.token_processor)
+            if self.cfg.clear_on_all_blocks_cleared:
+                self.index.apply_event_batches(
+                    batches, self.token_processor,
+                    clear_on_all_blocks_cleared=True)
+            else:
+                self.index.apply_event_batches(batches, self.token_processor)
         except Exception:
             logger.exception("on-device event application failed; "
                              "falling back to per-event path")
@@ -195,8 +204,10 @@ class EventsPool:
         self.digest_events(msg.pod_identifier, msg.model_name, batch.events)
 
     def digest_events(self, pod_identifier: str, model_name: str, events) -> None:
-        digest_events(self.index, self.token_processor, pod_identifier,
-                      model_name, events)
+        digest_events(
+            self.index, self.token_processor, pod_identifier, model_name,
+            events,
+            clear_on_all_blocks_cleared=self.cfg.clear_on_all_blocks_cleared)
 
 
 def _tier(medium: Optional[str]) -> str:
@@ -204,9 +215,14 @@ def _tier(medium: Optional[str]) -> str:
 
 
 def digest_events(index: Index, token_processor: ChunkedTokenDatabase,
-                  pod_identifier: str, model_name: str, events) -> None:
+                  pod_identifier: str, model_name: str, events,
+                  clear_on_all_blocks_cleared: bool = False) -> None:
     """Apply decoded events to an index (pool.go:246-338 semantics);
-    usable standalone by the tiered index and the sharded service."""
+    usable standalone by the tiered index and the sharded service.
+
+    clear_on_all_blocks_cleared: AllBlocksCleared purges this pod's
+    entries for this model at the event's position (the pod keeps its
+    id); off, the event is the reference's no-op."""
     logger.debug("digesting %d events from %s/%s", len(events),
                  pod_identifier, model_name)
     for ev in events:
@@ -216,6 +232,12 @@ def digest_events(index: Index, token_processor: ChunkedTokenDatabase,
         elif isinstance(ev, BlockRemoved):
             _digest_block_removed(index, pod_identifier, model_name, ev)
         elif isinstance(ev, AllBlocksCleared):
+            if clear_on_all_blocks_cleared:
+                try:
+                    index.clear_pods([pod_identifier], model_name)
+                except Exception as e:
+                    logger.debug("failed to clear pod %s: %s",
+                                 pod_identifier, e)
             continue
         else:
             logger.debug("unknown event %r from %s", ev, pod_identifier)

@@ -368,6 +368,19 @@ void kvidx::cpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
   }
 }
 
+// Purge by pod: the sweep itself is purge_pods_host (kvidx_common.h,
+// torch-free so that a stand-alone sanitizer build can call it).
+std::vector<int64_t> kvidx::cpu_purge_pods(KVIDX_TABLE_PARAMS,
+                                           at::Tensor purge_words,
+                                           int64_t model_id) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
+  const int W = purge_words_checked(purge_words, model_id);
+  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
+              "pods must hold capacity * pods_per_key entries");
+  const PurgeCounts c = purge_pods_host(v, u64p(purge_words), W, model_id);
+  return {c.entries_cleared, c.keys_tombstoned};
+}
+
 // found: 0 absent, 1 present-with-visible-pods, 2 present-but-empty
 // (chain-cut marker, in_memory.go:118-121).
 std::vector<at::Tensor> kvidx::cpu_lookup(KVIDX_TABLE_PARAMS,

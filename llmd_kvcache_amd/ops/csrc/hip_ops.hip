@@ -304,6 +304,143 @@ __global__ void k_evict(Table v, const uint64_t* __restrict__ eh,
   dev_remove_pods(v, eh[i], model, entries, n_entries);
 }
 
+// ---- purge by pod ------------------------------------------------------
+// One sweep over pods[C * P] read as the flat array it is.  A workgroup
+// takes tiles of PURGE_ROWS whole table rows: PURGE_ROWS * P dwords start
+// on a 1 KB boundary whatever P is, so a tile is read as 16-byte vectors,
+// consecutive lanes taking consecutive vectors, and no row leaves its
+// tile.  Inside the tile rows do straddle vectors and waves (P = 10: a row
+// is 2.5 vectors), so the lane that holds a dword is not the lane that
+// decides about its row: every lane reports what it saw of a row to that
+// row's flag word in LDS (ROW_HIT: cleared an entry; ROW_LIVE: an entry
+// remains), and after a barrier thread r reads row r's flags and
+// tombstones the row if it was hit and nothing remains.  Nothing is read
+// from global memory twice.  The tile's meta words (slot eligibility) and
+// the purge bitmap (<= 512 B) sit in LDS as well: neighbouring lanes ask
+// for the same or the next row (broadcast or distinct banks), and the
+// bitmap test is one data-dependent ds_read_b32 for the few entries that
+// are not empty.
+constexpr int PURGE_THREADS = 256;
+constexpr int PURGE_ROWS = 256;        // rows per tile: one per thread
+constexpr int PURGE_VECS = 4;          // 16-byte loads in flight per thread
+constexpr int PURGE_MAX_BLOCKS = 2048; // 8 workgroups on each of 256 CUs
+constexpr uint32_t ROW_HIT = 1u, ROW_LIVE = 2u;
+
+// One pod entry e read from *p, which lies in tile row `row`.
+DEV void purge_entry(uint32_t e, uint32_t* p, int row,
+                     const uint32_t* s_bits, uint32_t n_bits,
+                     const uint32_t* s_meta, int model_id, uint32_t* s_flags,
+                     uint32_t& n_cleared) {
+  if (e == 0) return;
+  const uint32_t pid = pod_entry_id(e);
+  bool cleared = false;
+  if (pid < n_bits && ((s_bits[pid >> 5] >> (pid & 31)) & 1) &&
+      purge_slot_eligible(s_meta[row], model_id))
+    // CAS, not a store: a concurrent dev_pod_set_add overwrite of this
+    // slot must survive, and then the row stays live
+    cleared = atomicCAS(p, e, 0u) == e;
+  n_cleared += cleared ? 1u : 0u;
+  atomicOr(&s_flags[row], cleared ? ROW_HIT : ROW_LIVE);
+}
+
+// bits: the purge bitmap as n_bit_words 32-bit words (pod id pid is bit
+// pid % 32 of word pid / 32).  model_id -1: every model.  partials
+// [gridDim.x][2]: each workgroup's {entries cleared, keys tombstoned},
+// written once with plain stores - the op sums them after its one
+// readback, so no counter has to be zeroed before the launch.
+__global__ void __launch_bounds__(PURGE_THREADS) k_purge_pods(
+    Table v, const uint32_t* __restrict__ bits, int n_bit_words, int model_id,
+    int64_t n_tiles, uint32_t* __restrict__ partials) {
+  __shared__ uint32_t s_bits[128];
+  __shared__ uint32_t s_meta[PURGE_ROWS];
+  __shared__ uint32_t s_flags[PURGE_ROWS];
+  __shared__ uint32_t s_red[2 * (PURGE_THREADS / 64)];
+  const int tid = threadIdx.x;
+  const uint32_t P = (uint32_t)v.pods_per_key;
+  const uint64_t cap = v.cap_mask + 1;
+  const uint32_t n_bits = (uint32_t)n_bit_words * 32u;
+  if (tid < n_bit_words) s_bits[tid] = bits[tid];
+  uint32_t n_cleared = 0, n_tomb = 0;
+
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const uint64_t row0 = (uint64_t)tile * PURGE_ROWS;
+    const uint64_t rows_left = cap - row0;
+    const int rows = rows_left < PURGE_ROWS ? (int)rows_left : PURGE_ROWS;
+    const uint32_t n_dw = (uint32_t)rows * P;
+    const uint32_t n_vec = n_dw >> 2;
+    uint32_t* tile_p = v.pods + row0 * P;
+    const uint4* tile_v = reinterpret_cast<const uint4*>(tile_p);
+
+    // the meta load goes out first and is the only one waited for before
+    // the barrier; the first PURGE_VECS vector loads stay in flight
+    const uint32_t m_mine = tid < rows ? v.meta[row0 + tid] : 0u;
+    uint32_t base = 0;
+    do {
+      uint4 q[PURGE_VECS];
+#pragma unroll
+      for (int k = 0; k < PURGE_VECS; ++k) {
+        const uint32_t vi = base + k * PURGE_THREADS + tid;
+        q[k] = vi < n_vec ? tile_v[vi] : make_uint4(0, 0, 0, 0);
+      }
+      if (base == 0) {
+        s_meta[tid] = m_mine;
+        s_flags[tid] = 0;
+        __syncthreads();
+      }
+#pragma unroll
+      for (int k = 0; k < PURGE_VECS; ++k) {
+        const uint32_t vi = base + k * PURGE_THREADS + tid;
+        if ((q[k].x | q[k].y | q[k].z | q[k].w) == 0) continue;
+        const uint32_t i0 = vi * 4;
+        uint32_t row = i0 / P;
+        uint32_t col = i0 - row * P;
+        const uint32_t e[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          purge_entry(e[j], tile_p + i0 + j, (int)row, s_bits, n_bits, s_meta,
+                      model_id, s_flags, n_cleared);
+          if (++col == P) { col = 0; ++row; }
+        }
+      }
+      base += PURGE_THREADS * PURGE_VECS;
+    } while (base < n_vec);
+    // a tile whose dword count is no multiple of 4 (capacity 1 or 2 only)
+    if ((uint32_t)tid < (n_dw & 3u)) {
+      const uint32_t i = n_vec * 4 + tid;
+      purge_entry(tile_p[i], tile_p + i, (int)(i / P), s_bits, n_bits, s_meta,
+                  model_id, s_flags, n_cleared);
+    }
+    __syncthreads();
+    // thread r owns row r: it wrote the row's meta and flag words and is
+    // the one to rewrite them for the next tile, so no third barrier
+    if (tid < rows && s_flags[tid] == ROW_HIT && !(s_meta[tid] & META_TOMB)) {
+      const uint32_t old = atomicOr(&v.meta[row0 + tid], META_TOMB);
+      n_tomb += (old & META_TOMB) ? 0u : 1u;
+    }
+  }
+
+  // counters: wave, then workgroup, then one pair of stores
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    n_cleared += __shfl_down(n_cleared, off, 64);
+    n_tomb += __shfl_down(n_tomb, off, 64);
+  }
+  if ((tid & 63) == 0) {
+    s_red[2 * (tid >> 6)] = n_cleared;
+    s_red[2 * (tid >> 6) + 1] = n_tomb;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t c = 0, t = 0;
+    for (int w = 0; w < PURGE_THREADS / 64; ++w) {
+      c += s_red[2 * w];
+      t += s_red[2 * w + 1];
+    }
+    partials[2 * blockIdx.x] = c;
+    partials[2 * blockIdx.x + 1] = t;
+  }
+}
+
 __global__ void k_get_request_keys(Table v,
                                    const uint64_t* __restrict__ eh, int64_t n,
                                    uint32_t model, uint8_t* __restrict__ found,
@@ -1173,6 +1310,40 @@ void kvidx::gpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
   if (n == 0) return;
   launch_1d(k_evict, n, v, u64p(engine_hashes), n, (uint32_t)model_id,
             u32p(pod_entries), (int)pod_entries.numel());
+}
+
+// One launch on the current stream, no fill before it; the only host wait
+// is the readback of the per-workgroup counters.
+std::vector<int64_t> kvidx::gpu_purge_pods(KVIDX_TABLE_PARAMS,
+                                           at::Tensor purge_words,
+                                           int64_t model_id) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  const int W = purge_words_checked(purge_words, model_id);
+  TORCH_CHECK(purge_words.device() == keys.device(),
+              "purge_words must live on the table's device");
+  TORCH_CHECK(pods_per_key >= 1 && pods_per_key <= 4096,
+              "pods_per_key out of range");
+  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
+              "pods must hold capacity * pods_per_key entries");
+  // tiles are read as 16-byte vectors from the start of the array
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
+              "pods storage must be 16-byte aligned");
+  const int64_t cap = keys.numel();
+  const int64_t n_tiles = (cap + PURGE_ROWS - 1) / PURGE_ROWS;
+  const int64_t grid = std::min<int64_t>(n_tiles, PURGE_MAX_BLOCKS);
+  auto partials = at::empty({grid, 2}, keys.options().dtype(at::kInt));
+  hipLaunchKernelGGL(k_purge_pods, dim3((unsigned)grid), dim3(PURGE_THREADS),
+                     0, STREAM, v,
+                     reinterpret_cast<const uint32_t*>(u64p(purge_words)),
+                     2 * W, (int)model_id, n_tiles, u32p(partials));
+  auto host = partials.cpu();  // waits for the sweep
+  const uint32_t* hp = u32p(host);
+  int64_t entries = 0, tombs = 0;
+  for (int64_t b = 0; b < grid; ++b) {
+    entries += hp[2 * b];
+    tombs += hp[2 * b + 1];
+  }
+  return {entries, tombs};
 }
 
 std::vector<at::Tensor> kvidx::gpu_get_request_keys(

@@ -582,6 +582,55 @@ KVIDX_HD int64_t probe_find(const uint64_t* __restrict__ keys,
   return -1;
 }
 
+// ---- purge by pod -----------------------------------------------------
+// A purge bitmap is W 64-bit words; bit pid % 64 of word pid / 64 selects
+// pod id pid.  Tier bits of an entry never take part.
+KVIDX_HD bool purge_selects(const uint64_t* words, int W, uint32_t e) {
+  const uint32_t pid = pod_entry_id(e);  // e == 0 -> 0xFFFFFFFF: no match
+  return e != 0 && pid < (uint32_t)W * 64u && ((words[pid >> 6] >> (pid & 63)) & 1);
+}
+// Does a slot with meta word m take part in a purge for model_id
+// (-1: every model)?  Tombstoned slots do: a stale entry left in one
+// would come back when the key is resurrected.
+KVIDX_HD bool purge_slot_eligible(uint32_t m, int64_t model_id) {
+  return (m & META_OCC) &&
+         (model_id < 0 || (int64_t)(m & META_MODEL_MASK) == model_id);
+}
+
+struct PurgeCounts {
+  int64_t entries_cleared = 0;
+  int64_t keys_tombstoned = 0;
+};
+
+// Host sweep: strip the selected pods from every eligible slot's pod set
+// and tombstone each live slot that this call emptied.  stamp, keys and
+// the engine map are untouched (the dev_remove_pods / cpu_evict stance).
+// Single writer; k_purge_pods is the device twin.
+inline PurgeCounts purge_pods_host(const Table& v, const uint64_t* words,
+                                   int W, int64_t model_id) {
+  PurgeCounts out;
+  for (uint64_t i = 0; i <= v.cap_mask; ++i) {
+    const uint32_t m = v.meta[i];
+    if (!purge_slot_eligible(m, model_id)) continue;
+    uint32_t* p = v.pods + i * (uint64_t)v.pods_per_key;
+    int cleared = 0, left = 0;
+    for (int k = 0; k < v.pods_per_key; ++k) {
+      if (purge_selects(words, W, p[k])) {
+        p[k] = 0;
+        ++cleared;
+      } else if (p[k] != 0) {
+        ++left;
+      }
+    }
+    out.entries_cleared += cleared;
+    if (cleared && !left && !(m & META_TOMB)) {
+      v.meta[i] = m | META_TOMB;
+      ++out.keys_tombstoned;
+    }
+  }
+  return out;
+}
+
 // Sharding: the main table holds only the keys a shard owns (the engine
 // map is replicated on every shard).
 KVIDX_HD bool owns_key(uint64_t h, int shard_id, int num_shards) {

@@ -44,6 +44,11 @@ void cpu_compact(KVIDX_TABLE_PARAMS, at::Tensor n_keys, at::Tensor n_meta,
                  at::Tensor n_e_meta, at::Tensor n_e_vals);
 void cpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes, int64_t model_id,
                at::Tensor pod_entries);
+// Purge by pod: purge_words int64 [W], 1 <= W <= 64, bit pid % 64 of word
+// pid / 64 selects pod id pid; model_id -1 = every model.
+// -> {entries_cleared, keys_tombstoned}.
+std::vector<int64_t> cpu_purge_pods(KVIDX_TABLE_PARAMS, at::Tensor purge_words,
+                                    int64_t model_id);
 std::vector<at::Tensor> cpu_lookup(KVIDX_TABLE_PARAMS,
                                    at::Tensor request_hashes, int64_t model_id,
                                    at::Tensor filter_words, int64_t num_pods,
@@ -70,6 +75,8 @@ void gpu_compact(KVIDX_TABLE_PARAMS, at::Tensor n_keys, at::Tensor n_meta,
                  at::Tensor n_e_meta, at::Tensor n_e_vals);
 void gpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes, int64_t model_id,
                at::Tensor pod_entries);
+std::vector<int64_t> gpu_purge_pods(KVIDX_TABLE_PARAMS, at::Tensor purge_words,
+                                    int64_t model_id);
 std::vector<at::Tensor> gpu_get_request_keys(KVIDX_TABLE_PARAMS,
                                              at::Tensor engine_hashes,
                                              int64_t model_id);
@@ -167,6 +174,19 @@ inline Table make_table_view(KVIDX_TABLE_PARAMS, bool on_gpu) {
   return Table{u64p(keys),   u32p(meta),   i32p(stamp),
                u32p(pods),   u64p(e_keys), u32p(e_meta),
                u64p(e_vals), (uint64_t)cap - 1, (int)pods_per_key};
+}
+
+// Word count of a purge bitmap, after the checks both purge ops share.
+inline int purge_words_checked(const at::Tensor& purge_words,
+                               int64_t model_id) {
+  TORCH_CHECK(purge_words.dtype() == at::kLong && purge_words.dim() == 1 &&
+                  purge_words.is_contiguous(),
+              "purge_words must be a contiguous int64 [W] tensor");
+  const int64_t W = purge_words.numel();
+  TORCH_CHECK(W >= 1 && W <= 64, "purge_words must hold 1..64 words");
+  TORCH_CHECK(model_id >= -1 && model_id <= (int64_t)META_MODEL_MASK,
+              "model_id out of range (-1 = every model)");
+  return (int)W;
 }
 
 // Runs f(std::integral_constant<int, ALGO>) for a native chain algo id

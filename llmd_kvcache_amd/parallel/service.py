@@ -14,6 +14,8 @@ collective, so raw payload bytes are shipped and decoded per rank.
 Protocol (collective ops driven by rank 0):
   ("events", [(pod, model, payload_bytes), ...])  apply on every rank
   ("score", hashes_i64_list, offsets, model, pods) score collectively
+  ("retire", pods)                                 purge + release ids
+  ("clear", pods, model)                           purge, ids kept
   ("stop",)                                        exit serve loops
 """
 
@@ -37,9 +39,14 @@ class ShardedIndexService:
         self,
         sharded: ShardedIndex,
         token_processor: Optional[ChunkedTokenDatabase] = None,
+        clear_on_all_blocks_cleared: bool = False,
     ):
+        """clear_on_all_blocks_cleared: an AllBlocksCleared event purges
+        its pod (EventsConfig option of the same name); it must be set
+        identically on every rank."""
         self.sharded = sharded
         self.token_processor = token_processor or ChunkedTokenDatabase()
+        self.clear_on_all_blocks_cleared = clear_on_all_blocks_cleared
         self.rank = sharded.rank
         self.group = sharded.group
         self._running = True
@@ -74,6 +81,13 @@ class ShardedIndexService:
             h = torch.tensor(hashes, dtype=torch.int64)
             offs = torch.tensor(offsets, dtype=torch.int32)
             return self.sharded.sharded_scores(h, offs, model, set(pods))
+        if kind == "retire":
+            # Broadcast ops run in one total order on every rank, so the
+            # ids come back at the same point of every rank's stream and
+            # lowest-free reuse hands them out identically afterwards.
+            return self.sharded.retire_pods(list(op[1]))
+        if kind == "clear":
+            return self.sharded.clear_pods(list(op[1]), op[2])
         if kind == "sync_check":
             # ROADMAP #8: loud detection of registry divergence before it
             # can misattribute merged-mask scores
@@ -89,15 +103,22 @@ class ShardedIndexService:
         if local.table.is_cuda:
             from ..kvblock.gpu_index import GpuIndex
 
-            GpuIndex.apply_event_batches.__get__(local)(
-                batches, self.token_processor
-            )
+            if self.clear_on_all_blocks_cleared:
+                GpuIndex.apply_event_batches.__get__(local)(
+                    batches, self.token_processor,
+                    clear_on_all_blocks_cleared=True)
+            else:
+                GpuIndex.apply_event_batches.__get__(local)(
+                    batches, self.token_processor
+                )
         else:
             from ..kvevents.pool import digest_events
 
             for pod, model, events in batches:
-                digest_events(local, self.token_processor, pod, model,
-                              events)
+                digest_events(
+                    local, self.token_processor, pod, model, events,
+                    clear_on_all_blocks_cleared=(
+                        self.clear_on_all_blocks_cleared))
 
     # -- rank-0 API ----------------------------------------------------
     def apply_messages(
@@ -137,6 +158,25 @@ class ShardedIndexService:
         self._broadcast(op)
         scores = self._dispatch(op)
         return self.sharded.local.scores_to_map(scores)[0]
+
+    def retire_pods(self, pods: Sequence[str]) -> Dict[str, object]:
+        """Purge these pods on every shard and release their ids, at one
+        point of the op order.  Returns rank 0's counts (its shard's).
+        Caller contract as TableIndex.retire_pods: no more events for
+        these pods are in flight."""
+        assert self.rank == 0
+        op = ("retire", sorted(set(pods)))
+        self._broadcast(op)
+        return self._dispatch(op)
+
+    def clear_pods(self, pods: Sequence[str],
+                   model_name: Optional[str] = None) -> Dict[str, object]:
+        """Purge these pods' entries (one model, or all) on every shard;
+        the pods keep their ids."""
+        assert self.rank == 0
+        op = ("clear", sorted(set(pods)), model_name)
+        self._broadcast(op)
+        return self._dispatch(op)
 
     def stop(self) -> None:
         assert self.rank == 0

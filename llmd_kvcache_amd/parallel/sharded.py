@@ -93,8 +93,26 @@ class ShardedIndex:
     def get_request_key(self, engine_key):
         return self.local.get_request_key(engine_key)
 
-    def apply_event_batches(self, batches, token_processor=None) -> None:
-        self.local.apply_event_batches(batches, token_processor)
+    def apply_event_batches(self, batches, token_processor=None,
+                            clear_on_all_blocks_cleared: bool = False) -> None:
+        if clear_on_all_blocks_cleared:
+            self.local.apply_event_batches(batches, token_processor,
+                                           clear_on_all_blocks_cleared=True)
+        else:
+            self.local.apply_event_batches(batches, token_processor)
+
+    def clear_pods(self, pods, model_name=None) -> dict:
+        """Purge the LOCAL shard.  Like add/evict, every rank calls this
+        with the same arguments at the same point of the op order; the
+        counts are this shard's."""
+        return self.local.clear_pods(pods, model_name)
+
+    def retire_pods(self, pods) -> dict:
+        """Purge the local shard and release the ids.  Registries are
+        replicated, so every rank must retire the same pods at the same
+        point of the op order (ShardedIndexService broadcasts it):
+        lowest-free id reuse then assigns the same ids everywhere."""
+        return self.local.retire_pods(pods)
 
     # -- read path -----------------------------------------------------
     def sharded_scores(

@@ -55,6 +55,10 @@ class AsgiIndexerApp:
             elif method == "POST" and path == "/score_chat_completions":
                 body = await self._read_json(receive)
                 await self._score_chat(send, body)
+            elif method == "POST" and path in ("/pods/clear",
+                                               "/pods/remove"):
+                body = await self._read_json(receive)
+                await self._pods_purge(send, body, path == "/pods/remove")
             elif method == "GET" and path == "/health":
                 await self._json(send, 200, {"status": "ok"})
             elif method == "GET" and path == "/metrics":
@@ -63,6 +67,8 @@ class AsgiIndexerApp:
                 await self._text(send, 404, "not found")
         except _BadRequest as e:
             await self._text(send, 400, str(e))
+        except NotImplementedError as e:  # backend cannot purge by pod
+            await self._text(send, 501, str(e))
         except Exception as e:  # pragma: no cover - defensive
             await self._text(send, 500, f"error: {e}")
 
@@ -124,6 +130,25 @@ class AsgiIndexerApp:
         pods = self.indexer.get_pod_scores(None, rendered, model, [])
         await self._json(send, 200, {"podScores": pods or {},
                                      "templated_messages": rendered})
+
+    async def _pods_purge(self, send, body: Dict[str, Any], remove: bool):
+        import asyncio
+
+        from .http_server import parse_pods_request
+
+        try:
+            pods, model = parse_pods_request(body)
+        except ValueError as e:
+            raise _BadRequest(str(e))
+        # a table sweep blocks until the device is done: off the loop
+        loop = asyncio.get_running_loop()
+        if remove:
+            out = await loop.run_in_executor(
+                None, self.indexer.remove_pods, pods)
+        else:
+            out = await loop.run_in_executor(
+                None, self.indexer.clear_pods, pods, model)
+        await self._json(send, 200, out)
 
     async def _metrics(self, send):
         from prometheus_client import generate_latest

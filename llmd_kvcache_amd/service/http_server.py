@@ -7,6 +7,12 @@
  - POST /score_chat_completions   chat-completions request -> {"podScores",
    "templated_messages"}  (template fetched for the model when absent)
  - GET  /metrics                  Prometheus exposition
+ - POST /pods/clear               {"pods": [...], "model": optional} -> drop
+                                  those pods' blocks, keep the pods
+ - POST /pods/remove              {"pods": [...]} -> retire the pods: drop
+                                  their blocks and release their ids
+   (both: 400 on a malformed body, 501 where the backend cannot purge by
+   pod; not in the reference, which never forgets a pod)
 
 Implemented on the stdlib http.server (threaded) to stay dependency-light
 and startable from tests; the env-config surface matches the reference
@@ -25,6 +31,21 @@ from ..indexer import Indexer
 from ..preprocessing import chat_completions as cc
 
 logger = logging.getLogger("llmd_kvcache_amd.http")
+
+
+def parse_pods_request(req):
+    """Body of POST /pods/clear and /pods/remove -> (pods, model or
+    None); ValueError on anything else (the fronts answer 400)."""
+    if not isinstance(req, dict):
+        raise ValueError("JSON object expected")
+    pods = req.get("pods")
+    if (not isinstance(pods, list) or not pods
+            or not all(isinstance(p, str) and p for p in pods)):
+        raise ValueError("field 'pods' (non-empty list of names) required")
+    model = req.get("model")
+    if model is not None and not isinstance(model, str):
+        raise ValueError("field 'model' must be a string")
+    return pods, (model or None)
 
 
 def make_handler(indexer: Indexer, coalescer=None):
@@ -81,10 +102,14 @@ def make_handler(indexer: Indexer, coalescer=None):
                     self._score_batch()
                 elif self.path == "/score_chat_completions":
                     self._score_chat_completions()
+                elif self.path in ("/pods/clear", "/pods/remove"):
+                    self._pods_purge(remove=self.path == "/pods/remove")
                 else:
                     self._send_error(404, "not found")
             except json.JSONDecodeError:
                 self._send_error(400, "invalid JSON body")
+            except NotImplementedError as e:
+                self._send_error(501, str(e))
             except Exception as e:
                 logger.exception("request failed")
                 self._send_error(500, f"error: {e}")
@@ -123,6 +148,19 @@ def make_handler(indexer: Indexer, coalescer=None):
             scores = indexer.score_tokens_batch(
                 token_lists, model, req.get("pods", []))
             self._send_json(200, {"scores": scores})
+
+        def _pods_purge(self, remove: bool):
+            req = self._read_json()
+            try:
+                pods, model = parse_pods_request(req)
+            except ValueError as e:
+                self._send_error(400, str(e))
+                return
+            if remove:
+                out = indexer.remove_pods(pods)
+            else:
+                out = indexer.clear_pods(pods, model)
+            self._send_json(200, out)
 
         def _score_chat_completions(self):
             req = self._read_json()
