@@ -103,6 +103,23 @@ def plan_read_route(offsets, block_size: int, hash_algo: str,
     return route
 
 
+def pack_token_lists(token_lists):
+    """Token lists -> (flat int64 tokens, int64 offsets [B+1]), the CPU
+    tensors score_flat_tokens and the wire front take."""
+    import numpy as np
+    import torch
+
+    lens = [len(t) for t in token_lists]
+    flat = np.empty(sum(lens), dtype=np.int64)
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    pos = 0
+    for i, t in enumerate(token_lists):
+        flat[pos:pos + lens[i]] = np.asarray(t, dtype=np.int64)
+        pos += lens[i]
+        off[i + 1] = pos
+    return torch.from_numpy(flat), torch.from_numpy(off)
+
+
 class Indexer:
     def __init__(
         self,
@@ -258,22 +275,9 @@ class Indexer:
             return self._score_keys_batch(keys_per_prompt, model_name,
                                           pod_identifiers)
 
-        import numpy as np
-        import torch
-
-        B = len(token_lists)
-        lens = [len(t) for t in token_lists]
-        flat = np.empty(sum(lens), dtype=np.int64)
-        off = np.zeros(B + 1, dtype=np.int64)
-        pos = 0
-        for i, t in enumerate(token_lists):
-            n = lens[i]
-            flat[pos:pos + n] = np.asarray(t, dtype=np.int64)
-            pos += n
-            off[i + 1] = pos
-        scores = self.score_flat_tokens(
-            torch.from_numpy(flat), torch.from_numpy(off), model_name,
-            pod_identifiers)
+        flat, off = pack_token_lists(token_lists)
+        scores = self.score_flat_tokens(flat, off, model_name,
+                                        pod_identifiers)
         return self._kv_block_index.scores_to_map(scores)
 
     def score_flat_tokens(
@@ -301,15 +305,12 @@ class Indexer:
         if route.device and route.max_k > 0:
             # raw tokens up, chain + probe + walk on the device: same
             # chain function, same walk, the same scores bit for bit
-            num_pods = idx._num_pods_padded()
+            a = idx.score_args(model_name, pod_identifiers,
+                               self.config.backend_configs)
             return idx.table.ops.gpu_score_flat_tokens(
-                *idx.table._t(), tokens_flat, offsets,
-                idx.registry.model_id(model_name),
-                idx._filter_tensor(set(pod_identifiers), num_pods),
-                idx.tier_weights(
-                    {b.name: b.weight for b in self.config.backend_configs}),
-                num_pods, idx.table.next_epoch(), init, bs,
-                max(1, len(idx.registry.id_to_tier)),
+                *idx.table._t(), tokens_flat, offsets, a.model_id,
+                a.filter_words, a.weights, a.num_pods,
+                idx.table.next_epoch(), init, bs, a.n_tiers,
                 hashing.NATIVE_ALGO_IDS[tp.config.hash_algo])
         parents = torch.full((B,), init, dtype=torch.int64)
         hashes, chunk_off = idx.table.ops.hash_chain_batch(

@@ -20,14 +20,20 @@ ids (Registry); the table stores only ids.
 from __future__ import annotations
 
 import heapq
+import os
 import threading
+from collections import namedtuple
+from contextlib import nullcontext
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
+import numpy as np
 import torch
 
 from ..scorer import default_kv_cache_backend_configs
 from ..utils import hashing
+from .event_batch import (FIELDS, FlatEvents, flatten_event_batches,
+                          plan_write_route)
 from .index import Index
 from .keys import Key, PodEntry
 
@@ -261,13 +267,13 @@ class KvTable:
                   num_pods, self.next_epoch(), shard_id, num_shards,
                   n_tiers)
 
-    def fused_score(self, hashes, counts_or_offsets, model_id, filter_words,
-                    weights, num_pods, max_k=None, n_tiers=MAX_TIERS):
+    def score_hashes(self, hashes, counts_or_offsets, model_id, filter_words,
+                     weights, num_pods, max_k=None, n_tiers=MAX_TIERS):
         if self.is_cuda:
-            # n_tiers (tiers actually registered) sizes the kernel's LDS:
-            # 1-2 real tiers instead of MAX_TIERS=4 keeps 256-pod fleets
-            # at 16-32 KB/WG and full occupancy.
-            return self.ops.gpu_fused_score(
+            # fused kernel, or lookup + mask walk where its LDS is too
+            # small.  n_tiers (tiers registered) sizes that LDS: 1-2 tiers
+            # keep 256-pod fleets at 16-32 KB/WG and full occupancy.
+            return self.ops.gpu_score_hashes(
                 *self._t(), hashes, counts_or_offsets, model_id, filter_words,
                 weights, num_pods, self.next_epoch(),
                 max_k if max_k is not None else 512, n_tiers)
@@ -331,6 +337,12 @@ class KvTable:
         self._epoch = int(state.get("epoch", 0))
 
 
+# TableIndex.score_args: num_pods is padded to whole 64-pod mask words,
+# filter_words int64 [W] (or [0]: every pod), weights float32 [MAX_TIERS]
+ScoreArgs = namedtuple("ScoreArgs",
+                       "model_id num_pods filter_words weights n_tiers")
+
+
 class TableIndex(Index):
     """Index contract over a KvTable (CPU or GPU device)."""
 
@@ -370,18 +382,29 @@ class TableIndex(Index):
     def _num_pods_padded(self) -> int:
         return max(64, (self.registry.num_pods + 63) // 64 * 64)
 
+    def score_args(self, model_name: str, pods, backend_configs=None,
+                   weights: Optional[torch.Tensor] = None) -> "ScoreArgs":
+        """What every probe/score op takes besides table and keys, staged
+        once.  pods: candidate filter (empty = all).  weights: the given
+        tensor, else from backend_configs (None = the default configs)."""
+        num_pods = self._num_pods_padded()
+        if weights is None:
+            weights = self.tier_weights(
+                None if backend_configs is None
+                else {b.name: b.weight for b in backend_configs})
+        return ScoreArgs(self.registry.model_id(model_name), num_pods,
+                         self._filter_tensor(set(pods), num_pods), weights,
+                         max(1, len(self.registry.id_to_tier)))
+
     # -- Index contract ------------------------------------------------
     def lookup(self, request_keys: Sequence[Key],
                pod_identifier_set: Set[str]) -> Dict[Key, List[PodEntry]]:
         if not request_keys:
             raise ValueError("no request keys provided for lookup")
-        model_id = self.registry.model_id(request_keys[0].model_name)
-        num_pods = self._num_pods_padded()
-        hashes = self._hashes_tensor(request_keys)
-        filt = self._filter_tensor(pod_identifier_set, num_pods)
+        a = self.score_args(request_keys[0].model_name, pod_identifier_set)
         found, masks = self.table.lookup(
-            hashes, model_id, filt, num_pods,
-            n_tiers=max(1, len(self.registry.id_to_tier)))
+            self._hashes_tensor(request_keys), a.model_id, a.filter_words,
+            a.num_pods, n_tiers=a.n_tiers)
         found = found.cpu().tolist()
         masks_l = masks.cpu().tolist()  # one bulk D2H/convert, no per-item
         W = masks.shape[2]
@@ -504,29 +527,12 @@ class TableIndex(Index):
         hashes: int64 flat request hashes; counts (CPU table) or offsets
         [B+1] int32 (GPU table). Returns float32 [B, num_pods] scores in
         registry pod-id order."""
-        model_id = self.registry.model_id(model_name)
-        num_pods = self._num_pods_padded()
-        filt = self._filter_tensor(pod_identifier_set, num_pods)
-        if weights is None:
-            weights = self.tier_weights()
-        if self.table.is_cuda:
-            W = (num_pods + 63) // 64
-            k = max_k if max_k is not None else 512
-            n_tiers = max(1, len(self.registry.id_to_tier))
-            if k * n_tiers * W * 8 > 64 * 1024:
-                # LDS would overflow (huge fleet x long prompts): fall back
-                # to the two-kernel path - global-mask lookup + mask walk.
-                found, masks = self.table.lookup(hashes, model_id, filt,
-                                                 num_pods, n_tiers=n_tiers)
-                del found
-                return self.table.ops.gpu_score_from_masks(
-                    masks.contiguous(), counts_or_offsets, weights, num_pods)
-            return self.table.fused_score(hashes, counts_or_offsets, model_id,
-                                          filt, weights, num_pods, max_k,
-                                          n_tiers=n_tiers)
-        with self._write_lock:
-            return self.table.fused_score(hashes, counts_or_offsets, model_id,
-                                          filt, weights, num_pods, max_k)
+        a = self.score_args(model_name, pod_identifier_set, weights=weights)
+        # CPU ops are single-writer
+        with nullcontext() if self.table.is_cuda else self._write_lock:
+            return self.table.score_hashes(
+                hashes, counts_or_offsets, a.model_id, a.filter_words,
+                a.weights, a.num_pods, max_k, a.n_tiers)
 
     def tier_weights(self, weight_map: Optional[Dict[str, float]] = None
                      ) -> torch.Tensor:
@@ -590,14 +596,6 @@ class TableIndex(Index):
         return out
 
 
-class _nullcontext:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 class _PinnedUploader:
     """Double-buffered pinned staging for event uploads.
 
@@ -629,12 +627,9 @@ class _PinnedUploader:
             while not ev.query():
                 _time.sleep(0)
 
-    def up(self, arr, name: str, device, dtype=None) -> torch.Tensor:
-        import numpy as np
-
-        if not isinstance(arr, np.ndarray):
-            arr = np.asarray(arr, dtype=dtype)
-        src = torch.from_numpy(np.ascontiguousarray(arr)).reshape(-1)
+    def up(self, arr, name: str, device, wait: bool = False) -> torch.Tensor:
+        # wait is the pageable uploader's: here the slot's event waits
+        src = torch.from_numpy(arr)
         n = src.numel()
         if n == 0:
             return torch.zeros(0, dtype=src.dtype, device=device)
@@ -654,6 +649,44 @@ class _PinnedUploader:
         if ev is None:
             ev = self._events[self._i] = torch.cuda.Event()
         ev.record()
+
+
+class _PageableUploader:
+    """Event uploads straight from pageable memory; nothing to rotate.
+    wait=True is torch.tensor(list, device=...)'s blocking copy, back once
+    the stream has drained: for the small arrays, not the payload."""
+
+    begin = end = staticmethod(lambda: None)
+
+    def up(self, arr, name: str, device, wait: bool = False) -> torch.Tensor:
+        return torch.from_numpy(arr).to(device, non_blocking=not wait)
+
+
+def _event_uploader(index):
+    """Pageable by default: on MI355X pinned+async stalls 38-96 ms now and
+    then (scripts/bench_upload.py).  KVIDX_PINNED=1 opts back in."""
+    if os.environ.get("KVIDX_PINNED", "0") != "1":
+        return _PageableUploader()
+    up = getattr(index, "_pinned_up", None)
+    if up is None:
+        up = index._pinned_up = _PinnedUploader()
+    return up
+
+
+def _upload_events(flat: FlatEvents, route, up, device) -> FlatEvents:
+    """flat's arrays as device tensors under the same names."""
+    if route.tokens_int32:
+        # int32 bit pattern of uint32 token ids: HALF the upload.  Kept in
+        # flat, so it lives until after the launch like every other array.
+        flat.tokens = flat.tokens.astype(np.uint32).view(np.int32)
+    dev = FlatEvents()
+    for name in FIELDS:
+        setattr(dev, name, up.up(getattr(flat, name), name, device,
+                                 wait=name not in ("tokens", "ehashes")))
+    if route.op != "gpu_apply_events":
+        flat.ev_of = flat.event_of_hash()
+        dev.ev_of = up.up(flat.ev_of, "ev_of", device)
+    return dev
 
 
 class NativeIndex(TableIndex):
@@ -727,241 +760,40 @@ class GpuIndex(TableIndex):
 
     def _apply_event_batches(self, batches: List[Tuple[str, str, list]],
                              token_processor=None) -> None:
-        from ..kvevents.events import (AllBlocksCleared, BlockRemoved,
-                                       BlockStored, get_hash_as_uint64)
-
+        """flatten -> plan (both in event_batch.py) -> upload -> launch."""
         if token_processor is None:
             from .token_processor import ChunkedTokenDatabase
 
             token_processor = ChunkedTokenDatabase()
-        block_size = token_processor.block_size
-        init_hash = token_processor.config.init_hash()
         # The kernels compute the request-key chain themselves, so they
         # must run the token processor's algorithm.  One without a native
-        # id cannot run on-device: raise, and kvevents.Pool falls back to
-        # its per-event Python path.
+        # id: raise, and kvevents.Pool falls back to its per-event path.
         hash_algo = token_processor.config.hash_algo
         algo_id = hashing.NATIVE_ALGO_IDS.get(hash_algo)
         if algo_id is None:
             raise ValueError(
                 f"hash_algo {hash_algo!r} has no native chain kernel; "
                 "apply these events through the per-event path")
-
-        import numpy as np
-
-        def _hashes_np(raw_list):
-            """Coerce a block-hash list to u64 bits as an int64 ndarray;
-            fast path for plain-int lists/ndarrays, per-element fallback
-            for mixed/bytes forms (pool.go:343-367 coercion)."""
-            try:
-                return np.asarray(raw_list, dtype=np.uint64).view(np.int64)
-            except (TypeError, ValueError, OverflowError):
-                out = []
-                for raw in raw_list:
-                    try:
-                        out.append(get_hash_as_uint64(raw))
-                    except Exception:
-                        continue
-                return np.asarray(out, dtype=np.uint64).view(np.int64)
-
-        token_arrays: List = []
-        n_tokens = 0
-        tok_off = [0]
-        hash_arrays: List = []
-        n_hashes = 0
-        eh_off = [0]
-        parents: List[int] = []
-        has_parent: List[int] = []
-        ev_type: List[int] = []
-        pod_entry: List[int] = []
-        grp_off = [0]
-        model_of: List[int] = []  # model id per event (mixed-model
-        # batches apply in ONE launch; the kernels read model_of[e])
-
-        by_pod: Dict[Tuple[str, str], list] = {}
-        order: List[Tuple[str, str]] = []
-        for pod, model, events in batches:
-            k = (pod, model)
-            if k not in by_pod:
-                by_pod[k] = []
-                order.append(k)
-            by_pod[k].extend(events)
-
-        for pod, model in order:
-            model_id = self.registry.model_id(model)
-            pod_id = self.registry.pod_id(pod)
-            n_events_in_group = 0
-            for ev in by_pod[(pod, model)]:
-                if isinstance(ev, BlockStored):
-                    # parse everything fallible BEFORE appending: a
-                    # malformed parent hash or an un-internable tier drops
-                    # the whole event, matching _digest_block_stored /
-                    # pool.go (CPU and GPU replicas converge on the same
-                    # state for malformed streams).
-                    if ev.parent_block_hash is not None:
-                        try:
-                            par = _to_i64(
-                                get_hash_as_uint64(ev.parent_block_hash))
-                            hp = 1
-                        except Exception:
-                            continue  # drop event (bad parent hash)
-                    else:
-                        par, hp = 0, 0
-                    try:
-                        tier = self.registry.tier_id(
-                            ev.medium.lower() if ev.medium else "gpu")
-                    except ValueError:
-                        continue  # drop event (tier registry full)
-                    hs = _hashes_np(ev.block_hashes)
-                    if hs.size == 0:
-                        continue
-                    hash_arrays.append(hs)
-                    n_hashes += hs.size
-                    eh_off.append(n_hashes)
-                    toks = np.asarray(ev.token_ids, dtype=np.int64)
-                    token_arrays.append(toks)
-                    n_tokens += toks.size
-                    tok_off.append(n_tokens)
-                    parents.append(par)
-                    has_parent.append(hp)
-                    ev_type.append(0)
-                    model_of.append(model_id)
-                    pod_entry.append((tier << 24) | (pod_id + 1))
-                    n_events_in_group += 1
-                elif isinstance(ev, BlockRemoved):
-                    try:
-                        tier = self.registry.tier_id(
-                            ev.medium.lower() if ev.medium else "gpu")
-                    except ValueError:
-                        continue  # drop event (tier registry full)
-                    hs = _hashes_np(ev.block_hashes)
-                    if hs.size == 0:
-                        continue
-                    hash_arrays.append(hs)
-                    n_hashes += hs.size
-                    eh_off.append(n_hashes)
-                    tok_off.append(n_tokens)
-                    parents.append(0)
-                    has_parent.append(0)
-                    ev_type.append(1)
-                    model_of.append(model_id)
-                    pod_entry.append((tier << 24) | (pod_id + 1))
-                    n_events_in_group += 1
-                elif isinstance(ev, AllBlocksCleared):
-                    continue
-            if n_events_in_group:
-                grp_off.append(grp_off[-1] + n_events_in_group)
-
-        if len(grp_off) == 1:
+        flat = flatten_event_batches(batches, self.registry)
+        if flat is None:
             return
-
-        d = self.device
-        tokens_np = (np.concatenate(token_arrays) if token_arrays
-                     else np.zeros(0, dtype=np.int64))
-        hashes_np = (np.concatenate(hash_arrays) if hash_arrays
-                     else np.zeros(0, dtype=np.int64))
-        import os as _os
-
-        # Default is PAGEABLE staging: measured on MI355X (ROCm 7.2,
-        # scripts/bench_upload.py) the pinned+async path is bimodal -
-        # ~0.1 ms typical for the 4 MB token upload but with sporadic
-        # 38-96 ms stalls in hipMemcpyAsync-from-pinned that crater
-        # ingest 9.9M -> 1.8M blocks/s, while pageable .to() is a steady
-        # ~0.1 ms (2.8 ms per 512-event batch end to end).  KVIDX_PINNED=1
-        # opts back in for stacks where the async path behaves.
-        if _os.environ.get("KVIDX_PINNED", "0") == "1":
-            up = getattr(self, "_pinned_up", None)
-            if up is None:
-                up = self._pinned_up = _PinnedUploader()
+        block_size = token_processor.block_size
+        route = plan_write_route(flat, block_size)
+        up = _event_uploader(self)
+        up.begin()
+        d = _upload_events(flat, route, up, self.device)
+        t = self.table
+        head = (*t._t(), d.tokens, d.tok_off, d.ehashes, d.eh_off, d.parents,
+                d.has_parent, d.ev_type, d.pod_entry)
+        tail = (_to_i64(token_processor.config.init_hash()), block_size,
+                t.next_epoch(), self.cfg.shard_id, self.cfg.num_shards)
+        if route.op == "gpu_apply_events":
+            t.ops.gpu_apply_events(*head, d.grp_off, d.model_of, *tail,
+                                   algo_id)
+        elif route.op == "gpu_apply_events_split":
+            t.ops.gpu_apply_events_split(*head, d.grp_off, d.ev_of,
+                                         d.model_of, *tail, algo_id)
         else:
-            up = None
-        # Kernel selection (host-side data only, BEFORE uploads):
-        #  - serial wave-per-group kernel when a batch both stores AND
-        #    removes some engine hash (per-pod op order matters);
-        #  - lane-per-EVENT transposed-chain kernel when no event's
-        #    parent is another event of THIS batch (chains independent
-        #    across events; parents resolve via the persistent engine
-        #    map): 8x the chain parallelism of lane-per-group, coalesced
-        #    int32 token loads, and HALF the token upload bytes;
-        #  - lane-per-group phase-split kernel otherwise.
-        use_split = True
-        if any(ev_type):
-            stored, removed = set(), set()
-            eh_list = hashes_np.tolist()
-            for e, t in enumerate(ev_type):
-                span = eh_list[eh_off[e]:eh_off[e + 1]]
-                (removed if t else stored).update(span)
-            use_split = not (stored & removed)
-        use_tr = use_split and block_size <= 64
-        if use_tr and any(has_parent):
-            par = np.asarray(parents, dtype=np.int64)[
-                np.asarray(has_parent, dtype=bool)]
-            if np.isin(par, hashes_np).any():
-                use_tr = False
-        if use_tr:
-            # int32 bit pattern of the flat tokens (uint32 token ids;
-            # HALF the upload); the [token_pos][event] transpose happens
-            # on-device (k_transpose_ev_tokens) - a host-side numpy
-            # transpose measured ~2-5 ms/batch and briefly halved ingest
-            lens = np.diff(np.asarray(tok_off, dtype=np.int64))
-            max_tokens = max(1, int(lens.max()) if len(lens) else 0)
-            tok_src = tokens_np.astype(np.uint32).view(np.int32)
-        else:
-            tok_src = tokens_np
-
-        if up is not None:
-            up.begin()
-            tok_t = up.up(tok_src, "tok", d)
-            common = (
-                up.up(tok_off, "tok_off", d, dtype=np.int32),
-                up.up(hashes_np, "eh", d),
-                up.up(eh_off, "eh_off", d, dtype=np.int32),
-                up.up(parents, "par", d, dtype=np.int64),
-                up.up(has_parent, "haspar", d, dtype=np.uint8),
-                up.up(ev_type, "evt", d, dtype=np.uint8),
-                up.up(pod_entry, "pe", d, dtype=np.int32),
-                up.up(grp_off, "grp", d, dtype=np.int32),
-                up.up(model_of, "mdl", d, dtype=np.int32),
-            )
-        else:
-            i32 = torch.int32
-            tok_t = torch.from_numpy(tok_src).to(d, non_blocking=True)
-            common = (
-                torch.tensor(tok_off, dtype=i32, device=d),
-                torch.from_numpy(hashes_np).to(d, non_blocking=True),
-                torch.tensor(eh_off, dtype=i32, device=d),
-                torch.tensor(parents, dtype=torch.int64, device=d),
-                torch.tensor(has_parent, dtype=torch.uint8, device=d),
-                torch.tensor(ev_type, dtype=torch.uint8, device=d),
-                torch.tensor(pod_entry, dtype=i32, device=d),
-                torch.tensor(grp_off, dtype=i32, device=d),
-                torch.tensor(model_of, dtype=i32, device=d),
-            )
-        if use_split:
-            counts = np.diff(np.asarray(eh_off, dtype=np.int64))
-            ev_of = np.repeat(np.arange(len(counts), dtype=np.int32), counts)
-            ev_of_t = (up.up(ev_of, "ev_of", d) if up is not None
-                       else torch.from_numpy(ev_of).to(d, non_blocking=True))
-            if use_tr:
-                self.table.ops.gpu_apply_events_split_tr(
-                    *self.table._t(), tok_t, *common[:7],
-                    ev_of_t, common[8], _to_i64(init_hash), block_size,
-                    self.table.next_epoch(), self.cfg.shard_id,
-                    self.cfg.num_shards, max_tokens, algo_id,
-                )
-            else:
-                self.table.ops.gpu_apply_events_split(
-                    *self.table._t(), tok_t, *common[:8], ev_of_t,
-                    common[8], _to_i64(init_hash), block_size,
-                    self.table.next_epoch(), self.cfg.shard_id,
-                    self.cfg.num_shards, algo_id,
-                )
-        else:
-            self.table.ops.gpu_apply_events(
-                *self.table._t(), tok_t, *common,
-                _to_i64(init_hash), block_size,
-                self.table.next_epoch(), self.cfg.shard_id,
-                self.cfg.num_shards, algo_id,
-            )
-        if up is not None:
-            up.end()
+            t.ops.gpu_apply_events_split_tr(*head, d.ev_of, d.model_of, *tail,
+                                            route.max_tokens, algo_id)
+        up.end()

@@ -184,14 +184,10 @@ class TieredIndex(Index):
         from .gpu_index import _to_u64
 
         hot = self.hot
-        model_id = hot.registry.model_id(model_name)
-        num_pods = hot._num_pods_padded()
-        filt = hot._filter_tensor(pod_identifier_set, num_pods)
-        if weights is None:
-            weights = hot.tier_weights()
-        n_tiers = max(1, len(hot.registry.id_to_tier))
-        found, masks = hot.table.lookup(hashes, model_id, filt, num_pods,
-                                        n_tiers=n_tiers)
+        a = hot.score_args(model_name, pod_identifier_set, weights=weights)
+        weights, num_pods = a.weights, a.num_pods
+        found, masks = hot.table.lookup(hashes, a.model_id, a.filter_words,
+                                        num_pods, n_tiers=a.n_tiers)
         if hot.table.is_cuda:
             offsets = counts_or_offsets
         else:  # CPU fused convention passes per-prompt counts

@@ -41,6 +41,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_lookup", &kvidx::gpu_lookup);
   m.def("gpu_fused_score", &kvidx::gpu_fused_score);
   m.def("gpu_score_from_masks", &kvidx::gpu_score_from_masks);
+  m.def("gpu_score_hashes", &kvidx::gpu_score_hashes);
   m.def("gpu_hash_chain", &kvidx::gpu_hash_chain,
         py::arg("tokens"), py::arg("tok_off"), py::arg("parents"),
         py::arg("block_size"), py::arg("algo") = 0);

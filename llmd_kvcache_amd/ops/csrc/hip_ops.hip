@@ -1126,8 +1126,9 @@ static const uint64_t* filter_ptr(const at::Tensor& filter_words) {
 }
 
 // The fused-score kernels hold a prompt's masks in LDS: up to 16 pod
-// words, 64 KB.  gpu_score_flat_tokens asks fused_score_fits to choose
-// its route; the launcher refuses what does not fit.
+// words, 64 KB.  gpu_score_hashes and gpu_score_flat_tokens ask
+// fused_score_fits to choose their route; the launcher refuses what does
+// not fit.
 static size_t fused_score_lds_bytes(int64_t max_k, int64_t n_tiers,
                                     int64_t W) {
   return (size_t)max_k * n_tiers * W * sizeof(uint64_t);
@@ -1434,6 +1435,22 @@ at::Tensor kvidx::gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
   return scores;
 }
 
+at::Tensor kvidx::gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                   at::Tensor offsets, int64_t model_id,
+                                   at::Tensor filter_words, at::Tensor weights,
+                                   int64_t num_pods, int64_t epoch,
+                                   int64_t max_k, int64_t n_tiers) {
+  if (fused_score_fits(max_k, clamp_tiers(n_tiers), pod_words(num_pods)))
+    return gpu_fused_score(KVIDX_TABLE_ARGS, hashes, offsets, model_id,
+                           filter_words, weights, num_pods, epoch, max_k,
+                           n_tiers);
+  // The masks do not fit in LDS (huge fleet, or long prompts on a large
+  // one; rare): masks in global memory, then the mask walk.
+  auto fm = gpu_lookup(KVIDX_TABLE_ARGS, hashes, model_id, filter_words,
+                       num_pods, epoch, 0, 1, n_tiers);
+  return gpu_score_from_masks(fm[1].contiguous(), offsets, weights, num_pods);
+}
+
 std::vector<at::Tensor> kvidx::gpu_hash_chain(
     at::Tensor tokens, at::Tensor tok_off, at::Tensor parents,
     int64_t block_size, int64_t algo) {
@@ -1559,9 +1576,11 @@ at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
     return gpu_fused_score_rows(KVIDX_TABLE_ARGS, hashes, staged[1], model_id,
                                 filter_words, weights, num_pods, epoch,
                                 p.max_k, n_tiers);
-  // The masks do not fit in LDS (huge fleet x long prompts; rare): gather
-  // the live slots of the rows into flat hashes and take the two-kernel
-  // path.  The gather index comes from the host's n_chunks, no wait.
+  // The masks do not fit in LDS: gather the live slots of the rows into
+  // flat hashes for gpu_score_hashes.  It asks fused_score_fits the same
+  // question again, so from here its fused branch is never taken: this
+  // is the two-kernel path.  The gather index comes from the host's
+  // n_chunks, no wait.
   auto idx_h = at::empty({p.total_chunks}, at::kLong);
   auto off_h = at::empty({p.B + 1}, at::kInt);
   {
@@ -1577,10 +1596,9 @@ at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
     op[p.B] = (int32_t)n;
   }
   auto flat = hashes.view({-1}).index_select(0, idx_h.to(dev));
-  auto fm = gpu_lookup(KVIDX_TABLE_ARGS, flat, model_id, filter_words,
-                       num_pods, epoch, 0, 1, n_tiers);
-  return gpu_score_from_masks(fm[1].contiguous(), off_h.to(dev), weights,
-                              num_pods);
+  return gpu_score_hashes(KVIDX_TABLE_ARGS, flat, off_h.to(dev), model_id,
+                          filter_words, weights, num_pods, epoch, p.max_k,
+                          n_tiers);
 }
 
 void kvidx::gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,

@@ -97,6 +97,15 @@ at::Tensor gpu_fused_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                                 int64_t n_tiers);
 at::Tensor gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
                                 at::Tensor weights, int64_t num_pods);
+// The one place that decides between the fused kernel and lookup + mask
+// walk: gpu_fused_score where its LDS holds the batch, else gpu_lookup
+// (unsharded) + gpu_score_from_masks.  hashes int64 flat, offsets int32
+// [B+1], both on the device.
+at::Tensor gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                            at::Tensor offsets, int64_t model_id,
+                            at::Tensor filter_words, at::Tensor weights,
+                            int64_t num_pods, int64_t epoch, int64_t max_k,
+                            int64_t n_tiers);
 std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
                                        at::Tensor parents, int64_t block_size,
                                        int64_t algo);

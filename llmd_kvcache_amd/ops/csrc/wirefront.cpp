@@ -1104,20 +1104,10 @@ at::Tensor wire_score_flat(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
   }
   if (max_k == 0)
     return at::zeros({B, num_pods}, at::kFloat);
-  int64_t W = (num_pods + 63) / 64;
-  at::Tensor scores;
-  if (max_k * n_tiers * W * 8 <= 64 * 1024) {
-    scores = gpu_fused_score(keys, meta, stamp, pods, e_keys, e_meta,
-                             e_vals, pods_per_key, h_dev, off_dev, model_id,
-                             filter_words, weights, num_pods, epoch, max_k,
-                             n_tiers);
-  } else {
-    auto fm = gpu_lookup(keys, meta, stamp, pods, e_keys, e_meta, e_vals,
-                         pods_per_key, h_dev, model_id, filter_words,
-                         num_pods, epoch, 0, 1, n_tiers);
-    scores = gpu_score_from_masks(fm[1].contiguous(), off_dev, weights,
-                                  num_pods);
-  }
+  auto scores = gpu_score_hashes(keys, meta, stamp, pods, e_keys, e_meta,
+                                 e_vals, pods_per_key, h_dev, off_dev,
+                                 model_id, filter_words, weights, num_pods,
+                                 epoch, max_k, n_tiers);
   return scores.to(at::kCPU, /*non_blocking=*/false).contiguous();
 #else
   TORCH_CHECK(false, "built without HIP but table is on GPU");

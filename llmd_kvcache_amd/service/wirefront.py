@@ -27,7 +27,7 @@ from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
-from ..indexer import Indexer, plan_read_route
+from ..indexer import Indexer, pack_token_lists, plan_read_route
 from ..utils import hashing
 
 
@@ -89,17 +89,11 @@ class WireIndexerService:
     def _stage(self, model: str, pods: Sequence[str]):
         idx = self.indexer.kv_block_index()
         tp = self.indexer.tokens_processor
-        model_id = idx.registry.model_id(model)
-        num_pods = idx._num_pods_padded()
-        filt = idx._filter_tensor(set(pods), num_pods)
-        weights = idx.tier_weights(
-            {b.name: b.weight
-             for b in self.indexer.config.backend_configs})
-        n_tiers = max(1, len(idx.registry.id_to_tier))
+        a = idx.score_args(model, pods, self.indexer.config.backend_configs)
         from ..kvblock.gpu_index import _to_i64
 
-        return (idx, model_id, filt, weights, num_pods, n_tiers,
-                _to_i64(tp.config.init_hash()), tp.block_size)
+        return (idx, a.model_id, a.filter_words, a.weights, a.num_pods,
+                a.n_tiers, _to_i64(tp.config.init_hash()), tp.block_size)
 
     def _device_chain(self, idx, offsets, bs) -> int:
         """The per-batch routing decision (indexer.plan_read_route) as
@@ -131,7 +125,6 @@ class WireIndexerService:
 
     def _score_text_cb(self, model: str, pods: Sequence[str],
                        prompts: List[str]):
-        import numpy as np
         import torch
 
         pool = self.indexer.tokenizers_pool
@@ -139,16 +132,7 @@ class WireIndexerService:
             token_lists = pool.tokenize_batch(list(prompts), model)
         else:  # custom pool injected without the batch API
             token_lists = [pool.tokenize(None, p, model) for p in prompts]
-        lens = [len(t) for t in token_lists]
-        flat = np.empty(sum(lens), dtype=np.int64)
-        off = np.zeros(len(token_lists) + 1, dtype=np.int64)
-        pos = 0
-        for i, t in enumerate(token_lists):
-            flat[pos:pos + lens[i]] = np.asarray(t, dtype=np.int64)
-            pos += lens[i]
-            off[i + 1] = pos
-        flat_t = torch.from_numpy(flat)
-        off_t = torch.from_numpy(off)
+        flat_t, off_t = pack_token_lists(token_lists)
         (idx, model_id, filt, weights, num_pods, n_tiers, init,
          bs) = self._stage(model, pods)
         scores = self._run_flat(

@@ -554,6 +554,52 @@ class TestLdsOverflowFallback:
             gpu.fused_scores(hashes, offs, MODEL, set(), max_k=K))
         assert maps[0] == {"pod-2000": float(K)}
 
+    @staticmethod
+    def _wide_fleet(index):
+        """1088 registered pods: 17 pod words, one more than the fused
+        kernel takes, under a 4-key prompt whose masks (4 keys x 2 tiers
+        x 17 words x 8 B) are nowhere near its 64 KB."""
+        for i in range(1088):
+            index.registry.pod_id(f"pod-{i}")
+        assert index._num_pods_padded() == 1088
+        return index
+
+    def test_wide_fleet_short_prompt_falls_back(self):
+        gpu = self._wide_fleet(
+            GpuIndex(GpuIndexConfig(capacity=1 << 12, pods_per_key=10)))
+        cpu = self._wide_fleet(
+            NativeIndex(TableIndexConfig(capacity=1 << 12, pods_per_key=10)))
+        K = 4
+        keys = [Key(MODEL, 50_000 + i) for i in range(K)]
+        for idx in (gpu, cpu):
+            idx.add(keys, keys, [PodEntry("pod-1080", "gpu")])
+        hashes = torch.tensor([_to_i64(k.chunk_hash) for k in keys],
+                              dtype=torch.int64)
+        got = gpu.scores_to_map(gpu.fused_scores(
+            hashes.cuda(), torch.tensor([0, K], dtype=torch.int32,
+                                        device="cuda"),
+            MODEL, set(), max_k=K))
+        want = cpu.scores_to_map(cpu.fused_scores(
+            hashes, torch.tensor([K], dtype=torch.int32), MODEL, set(),
+            max_k=K))
+        assert got[0] == {"pod-1080": 4.0}
+        assert got == want
+
+    def test_wide_fleet_short_prompt_through_indexer(self):
+        from llmd_kvcache_amd.indexer import Config, Indexer
+
+        gpu = self._wide_fleet(
+            GpuIndex(GpuIndexConfig(capacity=1 << 12, pods_per_key=10)))
+        indexer = Indexer(
+            Config(token_processor=TokenProcessorConfig(block_size=4)),
+            kv_block_index=gpu)
+        tokens = list(range(100, 116))
+        keys = indexer.tokens_processor.tokens_to_kv_block_keys(
+            None, tokens, MODEL)
+        assert len(keys) == 4
+        gpu.add(keys, keys, [PodEntry("pod-1080", "gpu")])
+        assert indexer.score_tokens(tokens, MODEL, []) == {"pod-1080": 4.0}
+
 
 class TestHighLoadFactor:
     def test_steal_path_under_pressure(self):
