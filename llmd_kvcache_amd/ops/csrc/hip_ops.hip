@@ -127,38 +127,80 @@ DEV void dev_pod_set_add(const Table& v, int64_t slot, uint32_t entry,
   atomicExch(&p[(uint32_t)epoch % v.pods_per_key], entry);  // full: overwrite
 }
 
+// Meta word of an engine-map slot whose key word is set, read past the L1
+// (another CU may have published it since this one cached the line).  A
+// writer that claimed the key word publishes the meta a store, a fence
+// and an atomic later, waiting for nobody, so an unpublished word is
+// polled: a bounded number of times, and the last word read is returned
+// either way.
+constexpr int EMAP_PUBLISH_POLLS = 1 << 12;
+DEV uint32_t dev_emap_published_meta(const uint32_t* p) {
+  uint32_t m = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int polls = 0; !(m & META_OCC) && polls < EMAP_PUBLISH_POLLS; ++polls) {
+    __builtin_amdgcn_s_sleep(1);
+    m = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return m;
+}
+
+// Engine map probe-or-insert, the device twin of cpu_ops.cpp's emap_put:
+// a slot is this writer's only if it holds (h, model).  A live slot with
+// the same key word under another model is somebody else's slot, like any
+// other key's: probed past, and at most the window's ordinary victim.
+// Free slots are claimed by atomicCAS on the key word, and racers of one
+// (hash, model) walk the same slots in the same order, so they end on one
+// slot.  A key word equal to h whose meta is not yet published belongs to
+// a racer mid-insert whose model is unknown: the meta is polled until it
+// is there (dev_emap_published_meta).  The claim publishes inside the
+// loop body, ahead of that poll and with no exit of its own, so that a
+// racer in the same wave has published before a lane of that wave polls.
+// If the poll runs out the slot counts as another model's.
 DEV void dev_emap_put(const Table& v, uint64_t h, uint32_t model,
                       uint64_t val) {
   h = remap_hash(h);
+  const uint32_t want = META_OCC | (model & META_MODEL_MASK);
   uint64_t s = probe_start(h, v.cap_mask);
   int64_t first_tomb = -1;
   int64_t victim = -1;
   for (int t = 0; t < PROBE_MAX; ++t) {
     uint64_t i = (s + t) & v.cap_mask;
     uint64_t k = v.e_keys[i];
+    int claimed = 0;
     if (k == 0) {
-      uint64_t prev = atomicCAS((unsigned long long*)&v.e_keys[i], 0ull,
-                                (unsigned long long)h);
-      if (prev == 0) {
+      k = atomicCAS((unsigned long long*)&v.e_keys[i], 0ull,
+                    (unsigned long long)h);
+      if (k == 0) {
         v.e_vals[i] = val;
         __threadfence();
-        atomicExch(&v.e_meta[i], META_OCC | (model & META_MODEL_MASK));
+        atomicExch(&v.e_meta[i], want);
+        claimed = 1;
+      }
+    }
+    // opaque to the optimizer: the publish above stays an if-then inside
+    // the loop instead of moving to a loop exit, which a wave runs only
+    // after its last lane has left the loop
+    asm volatile("" : "+v"(claimed)::"memory");
+    if (claimed) return;
+    uint32_t m;
+    if (k == h) {
+      m = dev_emap_published_meta(&v.e_meta[i]);
+      if ((m & META_OCC) && (m & META_TOMB)) {
+        // our key, dead: whoever swings the meta word owns the slot
+        if (atomicCAS(&v.e_meta[i], m, want) == m) {
+          v.e_vals[i] = val;
+          return;
+        }
+        m = __hip_atomic_load(&v.e_meta[i], __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if ((m & META_OCC) && !(m & META_TOMB) &&
+          (m & META_MODEL_MASK) == (model & META_MODEL_MASK)) {
+        v.e_vals[i] = val;  // refresh value (idempotent for same chain)
         return;
       }
-      k = prev;
+    } else {
+      m = v.e_meta[i];
     }
-    if (k == h) {
-      uint32_t m = v.e_meta[i];
-      if ((m & META_OCC) && (m & META_TOMB)) {
-        v.e_vals[i] = val;
-        __threadfence();
-        atomicExch(&v.e_meta[i], META_OCC | (model & META_MODEL_MASK));
-      } else {
-        v.e_vals[i] = val;  // refresh value (idempotent for same chain)
-      }
-      return;
-    }
-    uint32_t m = v.e_meta[i];
     if (m & META_TOMB) {
       if (first_tomb < 0) first_tomb = (int64_t)i;
     } else if ((m & META_OCC) && victim < 0) {
@@ -900,48 +942,86 @@ __global__ void k_apply_events(
 // stored and removed falls back to the serial kernel.
 // ---------------------------------------------------------------------
 
-// Batch-local engine-hash -> global block index map (open addressing,
-// zeroed tensors per call; value = idx+1 so 0 means empty).
-__global__ void k_batch_bmap(const uint64_t* __restrict__ ehashes, int64_t n,
+// Batch map: (group, engine hash) -> global block index, for the blocks
+// of the burst's KEPT BlockStored events only (open addressing, zeroed
+// tensors per call; value = idx+1).  Removed blocks and the blocks of an
+// event that event_chain_len drops never get a request key, so they are
+// not in it: a parent that names one resolves through the persistent
+// engine map like any other.  The group is part of the key word, so the
+// 128 pods of a fleet that store one hash in one burst take 128 scattered
+// slots, not one probe window.  Every block claims a slot of its own (no
+// deduplication); two key words may also collide, so a finder checks the
+// block an entry points to.  A block that finds no slot in its window is
+// left out, and a parent naming it resolves through the engine map.
+DEV uint64_t bmap_key(uint64_t h, int g) {
+  // odd multiplier: for one hash, distinct groups give distinct words
+  return remap_hash(h ^ ((uint64_t)(g + 1) * 0xD6E8FEB86659FD93ull));
+}
+
+// Group of event e: the g with grp_off[g] <= e < grp_off[g + 1].
+DEV int dev_group_of_event(const int32_t* __restrict__ grp_off, int G, int e) {
+  int lo = 0, hi = G - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (grp_off[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ void k_batch_bmap(const uint64_t* __restrict__ ehashes,
+                             const int32_t* __restrict__ eh_off,
+                             const int32_t* __restrict__ ev_of,
+                             const uint8_t* __restrict__ ev_type,
+                             const int32_t* __restrict__ tok_off,
+                             const int32_t* __restrict__ grp_off, int G,
+                             int block_size, int64_t n,
                              uint64_t* __restrict__ bkeys,
                              int32_t* __restrict__ bvals, int64_t bmask) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint64_t h = remap_hash(ehashes[i]);
-  uint64_t s = probe_start(h, (uint64_t)bmask);
+  const int e = ev_of[i];
+  if (ev_type[e] == 1) return;  // BlockRemoved
+  if (event_chain_len(tok_off, eh_off, e, block_size) < 0) return;
+  const uint64_t key = bmap_key(ehashes[i], dev_group_of_event(grp_off, G, e));
+  uint64_t s = probe_start(key, (uint64_t)bmask);
   for (int t = 0; t < PROBE_MAX; ++t) {
     uint64_t j = (s + t) & (uint64_t)bmask;
     uint64_t prev = atomicCAS((unsigned long long*)&bkeys[j], 0ull,
-                              (unsigned long long)h);
+                              (unsigned long long)key);
     if (prev == 0) {
       bvals[j] = (int32_t)(i + 1);  // consumers run in a later kernel
       return;
     }
-    if (prev == h) return;  // duplicate hash: first writer's index stands
   }
 }
 
+// Latest block in [lo, hi) that group g's kept stores gave engine hash h,
+// or -1.  [lo, hi) lies inside g's blocks: from its first block up to the
+// asking event's own.
 DEV int64_t dev_bmap_find(const uint64_t* __restrict__ bkeys,
                           const int32_t* __restrict__ bvals, int64_t bmask,
-                          uint64_t h) {
-  h = remap_hash(h);
-  uint64_t s = probe_start(h, (uint64_t)bmask);
+                          const uint64_t* __restrict__ ehashes, uint64_t h,
+                          int g, int64_t lo, int64_t hi) {
+  const uint64_t key = bmap_key(h, g);
+  uint64_t s = probe_start(key, (uint64_t)bmask);
+  int64_t best = -1;
   for (int t = 0; t < PROBE_MAX; ++t) {
     uint64_t j = (s + t) & (uint64_t)bmask;
     uint64_t k = bkeys[j];
-    if (k == 0) return -1;
-    if (k == h) {
-      int32_t v = bvals[j];
-      return v > 0 ? (int64_t)v - 1 : -1;
-    }
+    if (k == 0) break;
+    if (k != key) continue;
+    const int64_t bi = (int64_t)bvals[j] - 1;
+    if (bi >= lo && bi < hi && bi > best && ehashes[bi] == h) best = bi;
   }
-  return -1;
+  return best;
 }
 
 // Phase A: one lane per pod-group walks its events in order computing
-// request-key chains into req_scratch.  Parent resolution: earlier block
-// of the SAME group in this batch (bmap) first, then the persistent
-// engine map (cross-batch), else the chain root.
+// request-key chains into req_scratch.  Parent resolution: the latest
+// earlier block of the SAME group in this batch that a kept store gave
+// the parent hash (bmap) first, then the persistent engine map
+// (cross-batch), else the chain root.  What ANOTHER group of the batch
+// stores is never a parent here: groups run concurrently.
 template <int ALGO>
 __global__ void k_event_chains(
     Table v, const int64_t* __restrict__ tokens,
@@ -963,12 +1043,13 @@ __global__ void k_event_chains(
     const int n_chunks = event_chain_len(tok_off, eh_off, e, block_size);
     if (n_chunks < 0) continue;
     const int64_t bi =
-        has_parent[e] ? dev_bmap_find(bkeys, bvals, bmask, parents[e]) : -1;
+        has_parent[e] ? dev_bmap_find(bkeys, bvals, bmask, ehashes, parents[e],
+                                      (int)g, grp_first_block, eh_off[e])
+                      : -1;
     const int64_t* t0 = tokens + tok_off[e];
-    uint64_t h = bi >= grp_first_block && bi < eh_off[e]
-                     ? req_scratch[bi]  // earlier event of this group
-                     : dev_event_parent(v, has_parent, parents, model_of, e,
-                                        init_hash);
+    uint64_t h = bi >= 0 ? req_scratch[bi]  // earlier event of this group
+                         : dev_event_parent(v, has_parent, parents, model_of,
+                                            e, init_hash);
     for (int c = 0; c < n_chunks; ++c) {
       h = chain_link<ALGO>(h, t0 + (int64_t)c * block_size, block_size);
       req_scratch[eh_off[e] + c] = h;
@@ -1697,10 +1778,12 @@ void kvidx::gpu_apply_events_split(KVIDX_TABLE_PARAMS, at::Tensor tokens,
   auto bvals = at::zeros({bcap}, ehashes.options().dtype(at::kInt));
   auto req_scratch = at::zeros({n}, ehashes.options());
 
-  launch_1d(k_batch_bmap, n, u64p(ehashes), n, u64p(bkeys), i32p(bvals),
-            bcap - 1);
   TORCH_CHECK(model_of.numel() == ev_type.numel(),
               "model_of must have one id per event");
+  TORCH_CHECK(ev_of.numel() == n, "ev_of must have one event per hash");
+  launch_1d(k_batch_bmap, n, u64p(ehashes), i32p(eh_off), i32p(ev_of),
+            u8p(ev_type), i32p(tok_off), i32p(grp_off), (int)G,
+            (int)block_size, n, u64p(bkeys), i32p(bvals), bcap - 1);
   dispatch_algo(algo, [&](auto A) {
     launch_1d(k_event_chains<decltype(A)::value>, G, v,
               tokens.data_ptr<int64_t>(), i32p(tok_off), u64p(ehashes),
