@@ -51,3 +51,6 @@ asan:
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=all -o build/purge_asan_check \
 	    scripts/purge_asan_check.cc && ./build/purge_asan_check
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	    -fno-sanitize-recover=all -o build/remap_asan_check \
+	    scripts/remap_asan_check.cc && ./build/remap_asan_check

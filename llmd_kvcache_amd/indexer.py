@@ -16,6 +16,7 @@ single HIP kernel (ops/csrc/kvidx_hip.hip); with the sharded parallel index
 
 from __future__ import annotations
 
+from contextlib import nullcontext
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -160,14 +161,34 @@ class Indexer:
         backends that cannot purge by pod (Redis/Valkey)."""
         return self._kv_block_index.clear_pods(list(pods), model_name)
 
-    def remove_pods(self, pods: Sequence[str]) -> Dict[str, object]:
+    def remove_pods(self, pods: Sequence[str],
+                    compact: bool = False) -> Dict[str, object]:
         """Retire pods that are gone for good (a rollout replaced them):
         their blocks are dropped and, on table-backed indexes, their ids
         return to the registry, so the pod-word width of the read path
         shrinks again.  The caller guarantees that no more events for
         these pods are in flight; a late event only re-interns the name
-        under a fresh id."""
+        under a fresh id.  compact=True also renumbers the surviving pods
+        downwards in the same sweep (see compact_pod_ids)."""
+        if compact:
+            return self._kv_block_index.retire_pods(list(pods), compact=True)
         return self._kv_block_index.retire_pods(list(pods))
+
+    def compact_pod_ids(self) -> Dict[str, object]:
+        """Renumber the live pods 0, 1, 2, ... on table-backed indexes, so
+        that the read path's pod-word width follows the number of live
+        pods even when the survivors of a rollout are its newest names.
+        Returns {"pods_moved", "entries_moved", "entries_cleared",
+        "keys_tombstoned", "num_pods", "pod_generation"}; backends without
+        dense ids return zeros and num_pods None."""
+        return self._kv_block_index.compact_pod_ids()
+
+    def _ids_shared(self):
+        """The index registry's shared id gate (pod ids do not change
+        inside), or a no-op on backends without dense ids."""
+        reg = getattr(self._kv_block_index, "registry", None)
+        gate = getattr(reg, "ids_shared", None)
+        return gate() if gate is not None else nullcontext()
 
     def get_pod_scores(
         self,
@@ -216,10 +237,11 @@ class Indexer:
             weights = idx.tier_weights(
                 {b.name: b.weight for b in self.config.backend_configs}
             )
-            scores = fused(hashes, counts, block_keys[0].model_name,
-                           set(pod_identifiers), weights,
-                           max_k=len(block_keys))
-            return idx.scores_to_map(scores)[0]
+            with self._ids_shared():  # id-ordered columns back to names
+                scores = fused(hashes, counts, block_keys[0].model_name,
+                               set(pod_identifiers), weights,
+                               max_k=len(block_keys))
+                return idx.scores_to_map(scores)[0]
 
         # 3. generic index lookup (empty filter set = all pods)
         key_to_pods = self._kv_block_index.lookup(
@@ -276,9 +298,10 @@ class Indexer:
                                           pod_identifiers)
 
         flat, off = pack_token_lists(token_lists)
-        scores = self.score_flat_tokens(flat, off, model_name,
-                                        pod_identifiers)
-        return self._kv_block_index.scores_to_map(scores)
+        with self._ids_shared():
+            scores = self.score_flat_tokens(flat, off, model_name,
+                                            pod_identifiers)
+            return self._kv_block_index.scores_to_map(scores)
 
     def score_flat_tokens(
         self,
@@ -290,7 +313,9 @@ class Indexer:
         """Core batched scorer over flat int64 token tensors: parallel
         C++ chain -> one fused probe/score, or on a GPU table, where
         plan_read_route says so, the chain on the device as well.
-        Returns the [B, num_pods] float32 score tensor (CPU or device)."""
+        Returns the [B, num_pods] float32 score tensor (CPU or device),
+        columns in pod-id order: hold the registry's ids_shared() around
+        this call and scores_to_map, or check registry.pod_generation."""
         import torch
 
         from .kvblock.gpu_index import _to_i64
@@ -363,6 +388,7 @@ class Indexer:
             counts_t = torch.tensor(offs, dtype=torch.int32, device=device)
         else:
             counts_t = torch.tensor(counts, dtype=torch.int32)
-        scores = fused(hashes, counts_t, model_name, set(pod_identifiers),
-                       weights, max_k=max(counts))
-        return idx.scores_to_map(scores)
+        with self._ids_shared():
+            scores = fused(hashes, counts_t, model_name,
+                           set(pod_identifiers), weights, max_k=max(counts))
+            return idx.scores_to_map(scores)

@@ -191,8 +191,11 @@ class CostAwareMemoryIndex(Index):
         return {"entries_cleared": entries_cleared,
                 "keys_tombstoned": keys_dropped, "pods": sorted(seen)}
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
-        return self.clear_pods(pods, None)
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
+        out = self.clear_pods(pods, None)
+        if compact:
+            out = {**self.compact_pod_ids(), **out}
+        return out
 
     @property
     def total_cost_bytes(self) -> int:

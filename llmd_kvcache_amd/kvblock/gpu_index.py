@@ -32,6 +32,7 @@ import torch
 
 from ..scorer import default_kv_cache_backend_configs
 from ..utils import hashing
+from ..utils.idgate import IdGate
 from .event_batch import (FIELDS, FlatEvents, flatten_event_batches,
                           plan_write_route)
 from .index import Index
@@ -59,10 +60,20 @@ class Registry:
     empty string in ``id_to_pod`` and is absent from ``pod_to_id``.
     ``pod_id`` reuses the LOWEST free id before growing - a deterministic
     policy, so replicated ranks fed the same stream agree - and trailing
-    free ids are trimmed, so ``num_pods`` shrinks again."""
+    free ids are trimmed, so ``num_pods`` shrinks again.
+
+    Ids of LIVE pods change only in ``apply_pod_compaction``.  Whoever
+    carries a pod id across calls - from name to launch, or from an
+    id-ordered result back to names - does so inside ``ids_shared()``;
+    the compaction runs inside ``ids_exclusive()``.  ``pod_generation``
+    counts the compactions applied: a caller who keeps an id-ordered
+    tensor (``fused_scores``) outside any such span compares it before
+    and after, and discards the tensor if it moved."""
 
     def __init__(self, tier_names: Optional[Sequence[str]] = None):
         self._lock = threading.Lock()
+        self._id_gate = IdGate()
+        self.pod_generation = 0
         self.pod_to_id: Dict[str, int] = {}
         self.id_to_pod: List[str] = []
         self._free_pod_ids: List[int] = []  # min-heap of holes in id_to_pod
@@ -142,6 +153,53 @@ class Registry:
                               if not p]
         heapq.heapify(self._free_pod_ids)
         self._trim_free_tail()
+
+    # -- renumbering ----------------------------------------------------
+    def ids_shared(self):
+        """Context manager: pod ids do not change inside (re-entrant)."""
+        return self._id_gate.shared
+
+    def ids_exclusive(self):
+        """Context manager: no ids_shared() span is open inside."""
+        return self._id_gate.exclusive
+
+    def plan_pod_compaction(self, dropping: Sequence[str] = ()
+                            ) -> Optional[List[int]]:
+        """The order-preserving map that closes every hole: remap[old] is
+        the new id of a live pod (the live ids in ascending order become
+        0, 1, 2, ...) and -1 for a free id.  A pure function of the
+        registry, so replicas fed the same stream plan the same map.
+        None if no hole lies below the highest live id.  Pods named in
+        `dropping` count as free already (retire and compact at once)."""
+        with self._lock:
+            drop = {self.pod_to_id[p] for p in dropping if p in self.pod_to_id}
+            remap, nxt, holes = [], 0, False
+            for pid, name in enumerate(self.id_to_pod):
+                if name and pid not in drop:
+                    remap.append(nxt)
+                    holes |= nxt != pid
+                    nxt += 1
+                else:
+                    remap.append(-1)
+            return remap if holes else None
+
+    def apply_pod_compaction(self, remap: Sequence[int]) -> None:
+        """Renumber by a plan_pod_compaction map (ids mapped to -1 are
+        forgotten) and bump pod_generation.  The caller holds
+        ids_exclusive() and has rewritten every table that shares this
+        registry."""
+        with self._lock:
+            if len(remap) != len(self.id_to_pod):
+                raise ValueError("remap does not match the pod id space")
+            live = [(new, self.id_to_pod[old])
+                    for old, new in enumerate(remap) if new >= 0]
+            names = [""] * (max((n for n, _ in live), default=-1) + 1)
+            for new, name in live:
+                if not name or names[new]:
+                    raise ValueError("remap is not a renumbering of live pods")
+                names[new] = name
+            self._set_pods(names)
+            self.pod_generation += 1
 
     def model_id(self, model: str) -> int:
         with self._lock:
@@ -256,6 +314,19 @@ class KvTable:
               else self.ops.cpu_purge_pods)
         entries, keys = fn(*self._t(), words.contiguous(), model_id)
         return int(entries), int(keys)
+
+    def remap_pods(self, remap: Sequence[int]) -> Tuple[int, int, int]:
+        """Rewrite pod ids in every pod set of the table: remap[old] is
+        the new id, -1 drops the entry, ids >= len(remap) stay; keys that
+        lose their last entry are tombstoned.  Returns (entries_moved,
+        entries_cleared, keys_tombstoned).  The caller keeps every other
+        writer off the table for the duration (the sweep uses plain
+        stores); on a GPU table it has completed when this returns."""
+        t = torch.as_tensor(remap, dtype=torch.int32).to(self.device)
+        fn = (self.ops.gpu_remap_pods if self.is_cuda
+              else self.ops.cpu_remap_pods)
+        moved, cleared, keys = fn(*self._t(), t.contiguous())
+        return int(moved), int(cleared), int(keys)
 
     def lookup(self, request_hashes, model_id, filter_words, num_pods,
                sharded=True, n_tiers=MAX_TIERS):
@@ -401,6 +472,10 @@ class TableIndex(Index):
                pod_identifier_set: Set[str]) -> Dict[Key, List[PodEntry]]:
         if not request_keys:
             raise ValueError("no request keys provided for lookup")
+        with self.registry.ids_shared():
+            return self._lookup(request_keys, pod_identifier_set)
+
+    def _lookup(self, request_keys, pod_identifier_set):
         a = self.score_args(request_keys[0].model_name, pod_identifier_set)
         found, masks = self.table.lookup(
             self._hashes_tensor(request_keys), a.model_id, a.filter_words,
@@ -446,18 +521,20 @@ class TableIndex(Index):
         model_id = self.registry.model_id(request_keys[0].model_name)
         eh = self._hashes_tensor(engine_keys)
         rh = self._hashes_tensor(request_keys)
-        pe = self._entries_tensor(entries)
-        with self._write_lock:
-            self.table.insert(eh, rh, model_id, pe, emap_write=write_emap)
+        with self.registry.ids_shared():
+            pe = self._entries_tensor(entries)
+            with self._write_lock:
+                self.table.insert(eh, rh, model_id, pe, emap_write=write_emap)
 
     def evict(self, engine_key: Key, entries: Sequence[PodEntry]) -> None:
         if not entries:
             raise ValueError("no entries provided for eviction from index")
         model_id = self.registry.model_id(engine_key.model_name)
         eh = self._hashes_tensor([engine_key])
-        pe = self._entries_tensor(entries)
-        with self._write_lock:
-            self.table.evict(eh, model_id, pe)
+        with self.registry.ids_shared():
+            pe = self._entries_tensor(entries)
+            with self._write_lock:
+                self.table.evict(eh, model_id, pe)
 
     def get_request_key(self, engine_key: Key) -> Optional[Key]:
         model_id = self.registry.model_id(engine_key.model_name)
@@ -498,13 +575,17 @@ class TableIndex(Index):
         tombstone the keys that become empty.  The pods keep their ids:
         they are alive and will report blocks again.  Unknown pod names
         are ignored.  One sweep over the table, on its device."""
-        with self._write_lock:
+        with self.registry.ids_shared(), self._write_lock:
             return self._purge_locked(pods, model_name)
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
         """clear_pods for all models, then give the pods' ids back to the
         registry (lowest-free reuse, trailing ids trimmed - the score
         width W shrinks again).
+
+        compact=True purges and renumbers in ONE sweep (the retired pods
+        map to -1, the survivors downwards) under the exclusive id gate;
+        the result then also carries compact_pod_ids()'s keys.
 
         The ids are released only after the sweep has completed on the
         device, and still under the write lock, so no entry of a released
@@ -512,10 +593,77 @@ class TableIndex(Index):
         no more events for a retired pod are in flight.  A late event is
         not an error - it re-interns the name under a fresh id - but what
         it stores stays until the pod is retired again."""
-        with self._write_lock:
+        if compact:
+            with self.registry.ids_exclusive(), self._write_lock:
+                return self._retire_compact_locked([self], pods)
+        with self.registry.ids_shared(), self._write_lock:
             out = self._purge_locked(pods, None)
             self.registry.release_pods(out["pods"])
             return out
+
+    # -- compact pod ids -----------------------------------------------
+    @staticmethod
+    def _remap_tables(tables: Sequence["TableIndex"], reg: "Registry",
+                      remap: Optional[List[int]]) -> dict:
+        """One remap sweep per table, then the one registry swap.  The
+        caller holds reg.ids_exclusive() and every table's write lock."""
+        out = {"pods_moved": 0, "entries_moved": 0, "entries_cleared": 0,
+               "keys_tombstoned": 0}
+        if remap is not None:
+            for idx in tables:
+                if idx.table.is_cuda:
+                    # kernels launched inside shared spans, on any stream
+                    torch.cuda.synchronize(idx.device)
+            for idx in tables:
+                moved, cleared, keys = idx.table.remap_pods(remap)
+                out["entries_moved"] += moved
+                out["entries_cleared"] += cleared
+                out["keys_tombstoned"] += keys
+            out["pods_moved"] = sum(1 for old, new in enumerate(remap)
+                                    if new >= 0 and new != old)
+            reg.apply_pod_compaction(remap)
+        out["num_pods"] = reg.num_pods
+        out["pod_generation"] = reg.pod_generation
+        return out
+
+    @staticmethod
+    def _compact_locked(tables: Sequence["TableIndex"]) -> dict:
+        reg = tables[0].registry
+        return TableIndex._remap_tables(tables, reg,
+                                        reg.plan_pod_compaction())
+
+    @staticmethod
+    def _retire_compact_locked(tables: Sequence["TableIndex"],
+                               pods: Sequence[str]) -> dict:
+        """retire_pods(compact=True) body over the tables that share one
+        registry; gate and write locks are the caller's."""
+        reg = tables[0].registry
+        known = sorted({p for p in pods if p in reg.pod_to_id})
+        remap = reg.plan_pod_compaction(dropping=known)
+        if remap is None and known:
+            # the retired pods hold the highest ids: nobody moves, but the
+            # sweep still has to drop their entries
+            drop = {reg.pod_to_id[p] for p in known}
+            remap = [-1 if i in drop or not name else i
+                     for i, name in enumerate(reg.id_to_pod)]
+        out = TableIndex._remap_tables(tables, reg, remap)
+        out["pods"] = known
+        return out
+
+    def compact_pod_ids(self) -> dict:
+        """Renumber the live pods 0, 1, 2, ... in id order, in one sweep
+        over the table, so that the score width W depends on how many
+        pods are alive and not on which ids they happen to hold.  Nothing
+        to do (no launch, zeros) when no hole lies below the highest live
+        id.  entries_cleared / keys_tombstoned are 0 unless a stale entry
+        of a free id was found - and dropped.
+
+        Takes the exclusive id gate: waits for every open ids_shared()
+        span, and on a GPU table for the kernels they launched.  Id-
+        ordered tensors from before the call (fused_scores) are void
+        afterwards; registry.pod_generation tells."""
+        with self.registry.ids_exclusive(), self._write_lock:
+            return self._compact_locked([self])
 
     # -- fast paths ----------------------------------------------------
     def fused_scores(self, hashes: torch.Tensor, counts_or_offsets: torch.Tensor,
@@ -526,7 +674,10 @@ class TableIndex(Index):
 
         hashes: int64 flat request hashes; counts (CPU table) or offsets
         [B+1] int32 (GPU table). Returns float32 [B, num_pods] scores in
-        registry pod-id order."""
+        registry pod-id order.  Callers that turn the columns back into
+        names (scores_to_map) hold registry.ids_shared() from before this
+        call until after that; one that keeps the tensor longer checks
+        registry.pod_generation."""
         a = self.score_args(model_name, pod_identifier_set, weights=weights)
         # CPU ops are single-writer
         with nullcontext() if self.table.is_cuda else self._write_lock:
@@ -774,6 +925,11 @@ class GpuIndex(TableIndex):
             raise ValueError(
                 f"hash_algo {hash_algo!r} has no native chain kernel; "
                 "apply these events through the per-event path")
+        with self.registry.ids_shared():  # from interning to the launch
+            GpuIndex._launch_event_batches(self, batches, token_processor,
+                                           algo_id)
+
+    def _launch_event_batches(self, batches, token_processor, algo_id):
         flat = flatten_event_batches(batches, self.registry)
         if flat is None:
             return

@@ -165,7 +165,10 @@ class InMemoryIndex(Index):
         return {"entries_cleared": entries_cleared,
                 "keys_tombstoned": keys_dropped, "pods": sorted(seen)}
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
-        """No id space to give back here: the same as clear_pods for all
-        models."""
-        return self.clear_pods(pods, None)
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
+        """No id space to give back (or to compact) here: the same as
+        clear_pods for all models."""
+        out = self.clear_pods(pods, None)
+        if compact:
+            out = {**self.compact_pod_ids(), **out}
+        return out

@@ -55,12 +55,27 @@ class Index:
         raise NotImplementedError(
             f"{type(self).__name__} cannot purge by pod")
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
         """clear_pods for all models, then forget the pods themselves
         (table-backed indexes give their pod ids back).  Caller contract:
-        no more events for a retired pod are in flight."""
+        no more events for a retired pod are in flight.  compact=True adds
+        compact_pod_ids() - on table-backed indexes in the same sweep -
+        and its keys to the result."""
         raise NotImplementedError(
             f"{type(self).__name__} cannot purge by pod")
+
+    # -- compact pod ids ------------------------------------------------
+    NO_DENSE_IDS = {"pods_moved": 0, "entries_moved": 0, "entries_cleared": 0,
+                    "keys_tombstoned": 0, "num_pods": None,
+                    "pod_generation": 0}
+
+    def compact_pod_ids(self) -> dict:
+        """Renumber the live pods densely from 0 (table-backed indexes:
+        one sweep over the table).  Returns {"pods_moved", "entries_moved",
+        "entries_cleared", "keys_tombstoned", "num_pods",
+        "pod_generation"}.  A backend that keys its entries by pod name has
+        nothing to renumber: zeros, and num_pods None."""
+        return dict(self.NO_DENSE_IDS)
 
 
 @dataclass

@@ -121,8 +121,14 @@ class InstrumentedIndex(Index):
                    model_name: Optional[str] = None) -> dict:
         return self._count_purge(self.inner.clear_pods(pods, model_name))
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
+        if compact:
+            return self._count_purge(self.inner.retire_pods(pods,
+                                                            compact=True))
         return self._count_purge(self.inner.retire_pods(pods))
+
+    def compact_pod_ids(self) -> dict:
+        return self._count_purge(self.inner.compact_pod_ids())
 
     def __getattr__(self, name):
         return getattr(self.inner, name)

@@ -221,7 +221,7 @@ class RedisIndex(Index):
                    model_name: Optional[str] = None) -> dict:
         raise NotImplementedError(self._PURGE_MSG)
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
         raise NotImplementedError(self._PURGE_MSG)
 
 

@@ -119,17 +119,67 @@ class TieredIndex(Index):
         return self._merge_purge([self.hot.clear_pods(pods, model_name),
                                   self.cold.clear_pods(pods, model_name)])
 
-    def retire_pods(self, pods: Sequence[str]) -> dict:
-        """Purge both tiers, then release the ids ONCE: the tiers share
-        one registry, so the second tier must still know the names when
-        its sweep runs.  With table tiers both write locks are held from
-        the first sweep to the release."""
+    def _table_tiers(self):
+        """(hot, cold) when both are tables on one registry, else None."""
         from .gpu_index import TableIndex
 
         shared = getattr(self.cold, "registry", None) is self.registry
         if (shared and isinstance(self.hot, TableIndex)
                 and isinstance(self.cold, TableIndex)):
-            with self.hot._write_lock, self.cold._write_lock:
+            return [self.hot, self.cold]
+        return None
+
+    @staticmethod
+    def _merge_compact(outs) -> dict:
+        out = {k: sum(o[k] for o in outs)
+               for k in ("pods_moved", "entries_moved", "entries_cleared",
+                         "keys_tombstoned")}
+        nums = [o["num_pods"] for o in outs if o["num_pods"] is not None]
+        out["num_pods"] = max(nums) if nums else None
+        out["pod_generation"] = max(o["pod_generation"] for o in outs)
+        return out
+
+    def compact_pod_ids(self) -> dict:
+        """Two table tiers on one registry: both tables are remapped,
+        under both write locks, before the one registry swap (lock order:
+        id gate, hot, cold).  Separate registries: each tier compacts its
+        own."""
+        from .gpu_index import TableIndex
+
+        tiers = self._table_tiers()
+        if tiers is not None:
+            with self.registry.ids_exclusive(), self.hot._write_lock, \
+                    self.cold._write_lock:
+                return TableIndex._compact_locked(tiers)
+        if getattr(self.cold, "registry", None) is self.registry:
+            # one registry, but a tier that is no table cannot be rewritten
+            raise NotImplementedError(
+                "compact_pod_ids needs table tiers on a shared registry")
+        return self._merge_compact([self.hot.compact_pod_ids(),
+                                    self.cold.compact_pod_ids()])
+
+    def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
+        """Purge both tiers, then release the ids ONCE: the tiers share
+        one registry, so the second tier must still know the names when
+        its sweep runs.  With table tiers both write locks are held from
+        the first sweep to the release.  compact=True: one remap sweep per
+        tier does the purge and the renumbering, under the exclusive id
+        gate."""
+        from .gpu_index import TableIndex
+
+        if compact:
+            tiers = self._table_tiers()
+            if tiers is not None:
+                with self.registry.ids_exclusive(), self.hot._write_lock, \
+                        self.cold._write_lock:
+                    return TableIndex._retire_compact_locked(tiers, pods)
+            out = self.retire_pods(pods)
+            return {**self.compact_pod_ids(), **out}
+        shared = getattr(self.cold, "registry", None) is self.registry
+        if (shared and isinstance(self.hot, TableIndex)
+                and isinstance(self.cold, TableIndex)):
+            with self.registry.ids_shared(), self.hot._write_lock, \
+                    self.cold._write_lock:
                 out = self._merge_purge(
                     [self.hot._purge_locked(pods, None),
                      self.cold._purge_locked(pods, None)])
@@ -178,6 +228,12 @@ class TieredIndex(Index):
         masks on-device. Any hot miss routes the batch through the
         generic merged lookup (which also promotes the cold hits back
         into HBM) and the Python scorer."""
+        with self.registry.ids_shared():  # names -> ids -> out[b, pid]
+            return self._fused_scores(hashes, counts_or_offsets, model_name,
+                                      pod_identifier_set, weights)
+
+    def _fused_scores(self, hashes, counts_or_offsets, model_name,
+                      pod_identifier_set, weights):
         import torch
 
         from ..scorer import LongestPrefixScorer

@@ -25,6 +25,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cpu_compact", &kvidx::cpu_compact);
   m.def("cpu_evict", &kvidx::cpu_evict);
   m.def("cpu_purge_pods", &kvidx::cpu_purge_pods);
+  m.def("cpu_remap_pods", &kvidx::cpu_remap_pods);
   m.def("cpu_lookup", &kvidx::cpu_lookup);
   m.def("cpu_fused_score", &kvidx::cpu_fused_score);
   m.def("cpu_score_from_masks", &kvidx::cpu_score_from_masks);
@@ -36,6 +37,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_evict", &kvidx::gpu_evict);
   // one launch; the GIL is released around it and the counter readback
   m.def("gpu_purge_pods", &kvidx::gpu_purge_pods,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("gpu_remap_pods", &kvidx::gpu_remap_pods,
         py::call_guard<py::gil_scoped_release>());
   m.def("gpu_get_request_keys", &kvidx::gpu_get_request_keys);
   m.def("gpu_lookup", &kvidx::gpu_lookup);

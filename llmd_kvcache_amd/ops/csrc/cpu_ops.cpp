@@ -381,6 +381,19 @@ std::vector<int64_t> kvidx::cpu_purge_pods(KVIDX_TABLE_PARAMS,
   return {c.entries_cleared, c.keys_tombstoned};
 }
 
+// Remap pod ids: the sweep is remap_pods_host (kvidx_common.h, torch-free
+// like the purge's).
+std::vector<int64_t> kvidx::cpu_remap_pods(KVIDX_TABLE_PARAMS,
+                                           at::Tensor remap) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
+  TORCH_CHECK(!remap.is_cuda(), "remap must be a CPU tensor");
+  const int n = remap_checked(remap);
+  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
+              "pods must hold capacity * pods_per_key entries");
+  const RemapCounts c = remap_pods_host(v, i32p(remap), n);
+  return {c.entries_moved, c.entries_cleared, c.keys_tombstoned};
+}
+
 // found: 0 absent, 1 present-with-visible-pods, 2 present-but-empty
 // (chain-cut marker, in_memory.go:118-121).
 std::vector<at::Tensor> kvidx::cpu_lookup(KVIDX_TABLE_PARAMS,

@@ -483,6 +483,137 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_purge_pods(
   }
 }
 
+// ---- remap pod ids -----------------------------------------------------
+// The purge's sweep with a code table in place of the bitmap: the same
+// tiles of PURGE_ROWS whole rows, the same 16-byte loads and per-row flag
+// words.  The table (remap_entry's codes, 2 B per id, only the n given)
+// is staged in LDS once per workgroup: 8 KB at n = 4096, 10 288 B static
+// LDS in all, and the translation is one data-dependent ds_read_u16 per
+// non-empty entry.  A moved entry reports ROW_LIVE, a dropped one ROW_HIT.
+//
+// The caller holds every other writer off (kvidx_ops.h), so entries and
+// meta are written with plain stores: a 16-byte vector in which a dword
+// changed goes back whole, once, by the lane that loaded it; one in which
+// nothing changed, and any all-zero vector, is not written.
+
+// One non-empty entry e of tile row `row`; returns what it becomes.
+DEV uint32_t remap_one(uint32_t e, int row, const uint16_t* s_codes,
+                       uint32_t n, const uint32_t* s_meta, uint32_t* s_flags,
+                       uint32_t& n_moved, uint32_t& n_cleared) {
+  // the map first: an entry that stays needs no look at its slot's meta
+  uint32_t ne = remap_entry(e, s_codes, n);
+  if (ne != e && !purge_slot_eligible(s_meta[row], -1)) ne = e;
+  n_cleared += ne == 0 ? 1u : 0u;
+  n_moved += (ne != 0 && ne != e) ? 1u : 0u;
+  atomicOr(&s_flags[row], ne == 0 ? ROW_HIT : ROW_LIVE);
+  return ne;
+}
+
+// remap: int32 [n], -1 = drop.  partials [gridDim.x][3]: each workgroup's
+// {entries moved, entries cleared, keys tombstoned}, as in k_purge_pods.
+__global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
+    Table v, const int32_t* __restrict__ remap, int n, int64_t n_tiles,
+    uint32_t* __restrict__ partials) {
+  __shared__ uint16_t s_codes[MAX_PODS];
+  __shared__ uint32_t s_meta[PURGE_ROWS];
+  __shared__ uint32_t s_flags[PURGE_ROWS];
+  __shared__ uint32_t s_red[3 * (PURGE_THREADS / 64)];
+  const int tid = threadIdx.x;
+  const uint32_t P = (uint32_t)v.pods_per_key;
+  const uint64_t cap = v.cap_mask + 1;
+  const uint32_t un = (uint32_t)n;
+  // two codes per lane and store; the first tile's barrier publishes them
+  for (int i = 2 * tid; i < n; i += 2 * PURGE_THREADS) {
+    const uint32_t lo = (uint32_t)(remap[i] + 1);
+    const uint32_t hi = i + 1 < n ? (uint32_t)(remap[i + 1] + 1) : 0u;
+    reinterpret_cast<uint32_t*>(s_codes)[i >> 1] = lo | (hi << 16);
+  }
+  uint32_t n_moved = 0, n_cleared = 0, n_tomb = 0;
+
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const uint64_t row0 = (uint64_t)tile * PURGE_ROWS;
+    const uint64_t rows_left = cap - row0;
+    const int rows = rows_left < PURGE_ROWS ? (int)rows_left : PURGE_ROWS;
+    const uint32_t n_dw = (uint32_t)rows * P;
+    const uint32_t n_vec = n_dw >> 2;
+    uint32_t* tile_p = v.pods + row0 * P;
+    uint4* tile_v = reinterpret_cast<uint4*>(tile_p);
+
+    const uint32_t m_mine = tid < rows ? v.meta[row0 + tid] : 0u;
+    uint32_t base = 0;
+    do {
+      uint4 q[PURGE_VECS];
+#pragma unroll
+      for (int k = 0; k < PURGE_VECS; ++k) {
+        const uint32_t vi = base + k * PURGE_THREADS + tid;
+        q[k] = vi < n_vec ? tile_v[vi] : make_uint4(0, 0, 0, 0);
+      }
+      if (base == 0) {
+        s_meta[tid] = m_mine;
+        s_flags[tid] = 0;
+        __syncthreads();
+      }
+#pragma unroll
+      for (int k = 0; k < PURGE_VECS; ++k) {
+        const uint32_t vi = base + k * PURGE_THREADS + tid;
+        if ((q[k].x | q[k].y | q[k].z | q[k].w) == 0) continue;
+        const uint32_t i0 = vi * 4;
+        uint32_t row = i0 / P;
+        uint32_t col = i0 - row * P;
+        uint32_t e[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+        bool changed = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (e[j] != 0) {
+            const uint32_t ne = remap_one(e[j], (int)row, s_codes, un, s_meta,
+                                          s_flags, n_moved, n_cleared);
+            changed |= ne != e[j];
+            e[j] = ne;
+          }
+          if (++col == P) { col = 0; ++row; }
+        }
+        // vi < n_vec here: a vector past the tile was loaded as zeros
+        if (changed) tile_v[vi] = make_uint4(e[0], e[1], e[2], e[3]);
+      }
+      base += PURGE_THREADS * PURGE_VECS;
+    } while (base < n_vec);
+    // a tile whose dword count is no multiple of 4 (capacity 1 or 2 only)
+    if ((uint32_t)tid < (n_dw & 3u)) {
+      const uint32_t i = n_vec * 4 + tid;
+      const uint32_t e = tile_p[i];
+      if (e != 0) {
+        const uint32_t ne = remap_one(e, (int)(i / P), s_codes, un, s_meta,
+                                      s_flags, n_moved, n_cleared);
+        if (ne != e) tile_p[i] = ne;
+      }
+    }
+    __syncthreads();
+    // thread r owns row r, as in the purge
+    if (tid < rows && s_flags[tid] == ROW_HIT && !(s_meta[tid] & META_TOMB)) {
+      v.meta[row0 + tid] = s_meta[tid] | META_TOMB;
+      ++n_tomb;
+    }
+  }
+
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    n_moved += __shfl_down(n_moved, off, 64);
+    n_cleared += __shfl_down(n_cleared, off, 64);
+    n_tomb += __shfl_down(n_tomb, off, 64);
+  }
+  if ((tid & 63) == 0) {
+    s_red[3 * (tid >> 6)] = n_moved;
+    s_red[3 * (tid >> 6) + 1] = n_cleared;
+    s_red[3 * (tid >> 6) + 2] = n_tomb;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    uint32_t s = 0;
+    for (int w = 0; w < PURGE_THREADS / 64; ++w) s += s_red[3 * w + tid];
+    partials[3 * blockIdx.x + tid] = s;
+  }
+}
+
 __global__ void k_get_request_keys(Table v,
                                    const uint64_t* __restrict__ eh, int64_t n,
                                    uint32_t model, uint8_t* __restrict__ found,
@@ -1426,6 +1557,37 @@ std::vector<int64_t> kvidx::gpu_purge_pods(KVIDX_TABLE_PARAMS,
     tombs += hp[2 * b + 1];
   }
   return {entries, tombs};
+}
+
+// The purge's launch shape; the map is validated on the host first (one
+// small readback of remap), the counters come back after the sweep.
+std::vector<int64_t> kvidx::gpu_remap_pods(KVIDX_TABLE_PARAMS,
+                                           at::Tensor remap) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  TORCH_CHECK(remap.device() == keys.device(),
+              "remap must live on the table's device");
+  const int n = remap_checked(remap);
+  TORCH_CHECK(pods_per_key >= 1 && pods_per_key <= 4096,
+              "pods_per_key out of range");
+  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
+              "pods must hold capacity * pods_per_key entries");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
+              "pods storage must be 16-byte aligned");
+  const int64_t cap = keys.numel();
+  const int64_t n_tiles = (cap + PURGE_ROWS - 1) / PURGE_ROWS;
+  const int64_t grid = std::min<int64_t>(n_tiles, PURGE_MAX_BLOCKS);
+  auto partials = at::empty({grid, 3}, keys.options().dtype(at::kInt));
+  hipLaunchKernelGGL(k_remap_pods, dim3((unsigned)grid), dim3(PURGE_THREADS),
+                     0, STREAM, v, i32p(remap), n, n_tiles, u32p(partials));
+  auto host = partials.cpu();  // waits for the sweep
+  const uint32_t* hp = u32p(host);
+  int64_t moved = 0, cleared = 0, tombs = 0;
+  for (int64_t b = 0; b < grid; ++b) {
+    moved += hp[3 * b];
+    cleared += hp[3 * b + 1];
+    tombs += hp[3 * b + 2];
+  }
+  return {moved, cleared, tombs};
 }
 
 std::vector<at::Tensor> kvidx::gpu_get_request_keys(

@@ -631,6 +631,71 @@ inline PurgeCounts purge_pods_host(const Table& v, const uint64_t* words,
   return out;
 }
 
+// ---- remap pod ids ----------------------------------------------------
+// A remap gives every pod id below n a fate: kept, moved to another id, or
+// dropped.  Both sweeps work from its 16-bit code table, codes[old] =
+// new id + 1 and 0 = drop: 8 KB at MAX_PODS, which is what the kernel
+// stages in LDS.
+static constexpr int MAX_PODS = 4096;
+
+// What entry e becomes under the map: e itself if it is empty, if its id
+// lies past the map, or if the id maps to itself; 0 if the id is dropped;
+// else the new id under e's own tier bits.  The one definition for the
+// host sweep and k_remap_pods.
+KVIDX_HD uint32_t remap_entry(uint32_t e, const uint16_t* codes, uint32_t n) {
+  const uint32_t pid = pod_entry_id(e);  // e == 0 -> 0xFFFFFFFF: past n
+  if (pid >= n) return e;
+  const uint32_t c = codes[pid];
+  return c ? ((e & 0xFF000000u) | c) : 0u;
+}
+
+// codes[0..n) from remap[0..n) (values -1..MAX_PODS-1, checked by the ops).
+inline void remap_codes(const int32_t* remap, int n, uint16_t* codes) {
+  for (int i = 0; i < n; ++i) codes[i] = (uint16_t)(remap[i] + 1);
+}
+
+struct RemapCounts {
+  int64_t entries_moved = 0;
+  int64_t entries_cleared = 0;
+  int64_t keys_tombstoned = 0;
+};
+
+// Host sweep: rewrite every entry of every occupied slot (tombstoned ones
+// too - purge_slot_eligible(m, -1)) by remap_entry, and tombstone each
+// live slot that lost an entry to this call and kept none.  An injective
+// map never puts one id into a row twice.  stamp, keys and the engine map
+// are untouched.  Single writer; k_remap_pods is the device twin.
+inline RemapCounts remap_pods_host(const Table& v, const int32_t* remap,
+                                   int n) {
+  uint16_t codes[MAX_PODS];
+  remap_codes(remap, n, codes);
+  RemapCounts out;
+  for (uint64_t i = 0; i <= v.cap_mask; ++i) {
+    const uint32_t m = v.meta[i];
+    if (!purge_slot_eligible(m, -1)) continue;
+    uint32_t* p = v.pods + i * (uint64_t)v.pods_per_key;
+    int cleared = 0, left = 0;
+    for (int k = 0; k < v.pods_per_key; ++k) {
+      const uint32_t e = p[k];
+      if (e == 0) continue;
+      const uint32_t ne = remap_entry(e, codes, (uint32_t)n);
+      if (ne == 0) {
+        ++cleared;
+      } else {
+        ++left;
+        out.entries_moved += ne != e;
+      }
+      if (ne != e) p[k] = ne;
+    }
+    out.entries_cleared += cleared;
+    if (cleared && !left && !(m & META_TOMB)) {
+      v.meta[i] = m | META_TOMB;
+      ++out.keys_tombstoned;
+    }
+  }
+  return out;
+}
+
 // Sharding: the main table holds only the keys a shard owns (the engine
 // map is replicated on every shard).
 KVIDX_HD bool owns_key(uint64_t h, int shard_id, int num_shards) {

@@ -49,6 +49,18 @@ void cpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes, int64_t model_id,
 // -> {entries_cleared, keys_tombstoned}.
 std::vector<int64_t> cpu_purge_pods(KVIDX_TABLE_PARAMS, at::Tensor purge_words,
                                     int64_t model_id);
+// Remap pod ids: remap int32 [n] contiguous, 1 <= n <= MAX_PODS, remap[old]
+// = new id in 0..MAX_PODS-1 or -1 = drop, the non-negative values pairwise
+// distinct.  Entries whose id is >= n stay.  Every occupied slot takes part,
+// whatever its model.  -> {entries_moved, entries_cleared, keys_tombstoned}.
+//
+// Concurrency contract - NOT the purge's: the caller guarantees that no
+// other writer touches the table for the duration (the registry's id gate,
+// held exclusively, provides this).  A remap is not idempotent, and an
+// insert that carries a pre-remap id and races with it cannot be repaired
+// by a compare-and-swap the way a raced purge can, so the sweeps use plain
+// stores.
+std::vector<int64_t> cpu_remap_pods(KVIDX_TABLE_PARAMS, at::Tensor remap);
 std::vector<at::Tensor> cpu_lookup(KVIDX_TABLE_PARAMS,
                                    at::Tensor request_hashes, int64_t model_id,
                                    at::Tensor filter_words, int64_t num_pods,
@@ -77,6 +89,8 @@ void gpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes, int64_t model_id,
                at::Tensor pod_entries);
 std::vector<int64_t> gpu_purge_pods(KVIDX_TABLE_PARAMS, at::Tensor purge_words,
                                     int64_t model_id);
+// remap on the table's device; the sweep has completed on return
+std::vector<int64_t> gpu_remap_pods(KVIDX_TABLE_PARAMS, at::Tensor remap);
 std::vector<at::Tensor> gpu_get_request_keys(KVIDX_TABLE_PARAMS,
                                              at::Tensor engine_hashes,
                                              int64_t model_id);
@@ -196,6 +210,29 @@ inline int purge_words_checked(const at::Tensor& purge_words,
   TORCH_CHECK(model_id >= -1 && model_id <= (int64_t)META_MODEL_MASK,
               "model_id out of range (-1 = every model)");
   return (int)W;
+}
+
+// Length of a pod-id remap, after the checks both remap ops share: shape,
+// range of every value, and injectivity of the non-negative ones (so no
+// row can end up holding one id twice).  The values are read on the host.
+inline int remap_checked(const at::Tensor& remap) {
+  TORCH_CHECK(remap.dtype() == at::kInt && remap.dim() == 1 &&
+                  remap.is_contiguous(),
+              "remap must be a contiguous int32 [n] tensor");
+  const int64_t n = remap.numel();
+  TORCH_CHECK(n >= 1 && n <= MAX_PODS, "remap must hold 1..", MAX_PODS,
+              " ids");
+  const at::Tensor host = remap.cpu();
+  const int32_t* r = host.data_ptr<int32_t>();
+  std::vector<uint8_t> taken(MAX_PODS, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(r[i] >= -1 && r[i] < MAX_PODS, "remap[", i, "] = ", r[i],
+                " is outside -1..", MAX_PODS - 1);
+    if (r[i] < 0) continue;
+    TORCH_CHECK(!taken[r[i]], "remap sends two ids to ", r[i]);
+    taken[r[i]] = 1;
+  }
+  return (int)n;
 }
 
 // Runs f(std::integral_constant<int, ALGO>) for a native chain algo id

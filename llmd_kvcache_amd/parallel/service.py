@@ -85,7 +85,13 @@ class ShardedIndexService:
             # Broadcast ops run in one total order on every rank, so the
             # ids come back at the same point of every rank's stream and
             # lowest-free reuse hands them out identically afterwards.
+            if len(op) > 2 and op[2]:  # optional trailing flag: compact
+                return self.sharded.retire_pods(list(op[1]), compact=True)
             return self.sharded.retire_pods(list(op[1]))
+        if kind == "compact":
+            # the plan is a pure function of the (replicated) registry, so
+            # applying it at one point of the order keeps the ranks equal
+            return self.sharded.compact_pod_ids()
         if kind == "clear":
             return self.sharded.clear_pods(list(op[1]), op[2])
         if kind == "sync_check":
@@ -155,17 +161,29 @@ class ShardedIndexService:
         offsets = [0, len(request_keys)]
         op = ("score", hashes, offsets, request_keys[0].model_name,
               sorted(pod_identifier_set))
-        self._broadcast(op)
-        scores = self._dispatch(op)
-        return self.sharded.local.scores_to_map(scores)[0]
+        with self.sharded.registry.ids_shared():
+            self._broadcast(op)
+            scores = self._dispatch(op)
+            return self.sharded.local.scores_to_map(scores)[0]
 
-    def retire_pods(self, pods: Sequence[str]) -> Dict[str, object]:
+    def retire_pods(self, pods: Sequence[str],
+                    compact: bool = False) -> Dict[str, object]:
         """Purge these pods on every shard and release their ids, at one
         point of the op order.  Returns rank 0's counts (its shard's).
         Caller contract as TableIndex.retire_pods: no more events for
-        these pods are in flight."""
+        these pods are in flight.  compact=True renumbers the survivors
+        in the same sweep, on every rank."""
         assert self.rank == 0
-        op = ("retire", sorted(set(pods)))
+        op = (("retire", sorted(set(pods)), True) if compact
+              else ("retire", sorted(set(pods))))
+        self._broadcast(op)
+        return self._dispatch(op)
+
+    def compact_pod_ids(self) -> Dict[str, object]:
+        """Renumber the live pods on every rank at one point of the op
+        order; returns rank 0's counts (its shard's)."""
+        assert self.rank == 0
+        op = ("compact",)
         self._broadcast(op)
         return self._dispatch(op)
 

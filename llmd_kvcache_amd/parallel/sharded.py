@@ -107,12 +107,21 @@ class ShardedIndex:
         counts are this shard's."""
         return self.local.clear_pods(pods, model_name)
 
-    def retire_pods(self, pods) -> dict:
+    def retire_pods(self, pods, compact: bool = False) -> dict:
         """Purge the local shard and release the ids.  Registries are
         replicated, so every rank must retire the same pods at the same
         point of the op order (ShardedIndexService broadcasts it):
         lowest-free id reuse then assigns the same ids everywhere."""
+        if compact:
+            return self.local.retire_pods(pods, compact=True)
         return self.local.retire_pods(pods)
+
+    def compact_pod_ids(self) -> dict:
+        """Renumber the pods of the LOCAL shard and its registry.  The
+        plan is a pure function of the registry and registries are
+        replicated, so ranks that call this at the same point of the op
+        order end up with the same ids; the counts are this shard's."""
+        return self.local.compact_pod_ids()
 
     # -- read path -----------------------------------------------------
     def sharded_scores(
@@ -293,10 +302,12 @@ class ShardedIndex:
             device=self.device,
         )
         offsets = torch.tensor([0, len(request_keys)], dtype=torch.int32)
-        scores = self.sharded_scores(
-            hashes, offsets, request_keys[0].model_name, pod_identifier_set
-        )
-        return self.local.scores_to_map(scores)[0]
+        with self.registry.ids_shared():
+            scores = self.sharded_scores(
+                hashes, offsets, request_keys[0].model_name,
+                pod_identifier_set
+            )
+            return self.local.scores_to_map(scores)[0]
 
 
 def _partition_prompts(offs_cpu: torch.Tensor, world: int) -> Tuple[int, ...]:

@@ -59,6 +59,8 @@ class AsgiIndexerApp:
                                                "/pods/remove"):
                 body = await self._read_json(receive)
                 await self._pods_purge(send, body, path == "/pods/remove")
+            elif method == "POST" and path == "/pods/compact":
+                await self._pods_compact(send, await self._read_raw(receive))
             elif method == "GET" and path == "/health":
                 await self._json(send, 200, {"status": "ok"})
             elif method == "GET" and path == "/metrics":
@@ -134,20 +136,40 @@ class AsgiIndexerApp:
     async def _pods_purge(self, send, body: Dict[str, Any], remove: bool):
         import asyncio
 
-        from .http_server import parse_pods_request
+        from .http_server import parse_compact_flag, parse_pods_request
 
         try:
             pods, model = parse_pods_request(body)
+            compact = parse_compact_flag(body) if remove else False
         except ValueError as e:
             raise _BadRequest(str(e))
         # a table sweep blocks until the device is done: off the loop
         loop = asyncio.get_running_loop()
-        if remove:
+        if remove and compact:
+            out = await loop.run_in_executor(
+                None, lambda: self.indexer.remove_pods(pods, compact=True))
+        elif remove:
             out = await loop.run_in_executor(
                 None, self.indexer.remove_pods, pods)
         else:
             out = await loop.run_in_executor(
                 None, self.indexer.clear_pods, pods, model)
+        await self._json(send, 200, out)
+
+    async def _pods_compact(self, send, raw: bytes):
+        """POST /pods/compact (empty or {} body): renumber the live pods
+        densely from 0; waits for open scoring spans and sweeps the
+        table, so off the loop."""
+        import asyncio
+
+        from .http_server import parse_compact_request
+
+        try:
+            parse_compact_request(raw)
+        except ValueError as e:
+            raise _BadRequest(str(e))
+        loop = asyncio.get_running_loop()
+        out = await loop.run_in_executor(None, self.indexer.compact_pod_ids)
         await self._json(send, 200, out)
 
     async def _metrics(self, send):
@@ -168,15 +190,20 @@ class AsgiIndexerApp:
                 return
 
     @staticmethod
-    async def _read_json(receive) -> Dict[str, Any]:
+    async def _read_raw(receive) -> bytes:
         chunks = []
         while True:
             message = await receive()
             chunks.append(message.get("body", b""))
             if not message.get("more_body"):
                 break
+        return b"".join(chunks)
+
+    @staticmethod
+    async def _read_json(receive) -> Dict[str, Any]:
+        raw = await AsgiIndexerApp._read_raw(receive)
         try:
-            body = json.loads(b"".join(chunks))
+            body = json.loads(raw)
         except Exception:
             raise _BadRequest("invalid JSON body")
         if not isinstance(body, dict):

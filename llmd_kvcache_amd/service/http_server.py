@@ -9,10 +9,19 @@
  - GET  /metrics                  Prometheus exposition
  - POST /pods/clear               {"pods": [...], "model": optional} -> drop
                                   those pods' blocks, keep the pods
- - POST /pods/remove              {"pods": [...]} -> retire the pods: drop
-                                  their blocks and release their ids
+ - POST /pods/remove              {"pods": [...], "compact": optional bool}
+                                  -> retire the pods: drop their blocks and
+                                  release their ids; "compact": true also
+                                  renumbers the surviving pods downwards in
+                                  the same sweep
    (both: 400 on a malformed body, 501 where the backend cannot purge by
    pod; not in the reference, which never forgets a pod)
+ - POST /pods/compact             empty or {} body -> renumber the live pods
+                                  densely from 0 (one table sweep); answers
+                                  {"pods_moved", "entries_moved",
+                                  "entries_cleared", "keys_tombstoned",
+                                  "num_pods", "pod_generation"}; num_pods is
+                                  null on backends without dense pod ids
 
 Implemented on the stdlib http.server (threaded) to stay dependency-light
 and startable from tests; the env-config surface matches the reference
@@ -46,6 +55,21 @@ def parse_pods_request(req):
     if model is not None and not isinstance(model, str):
         raise ValueError("field 'model' must be a string")
     return pods, (model or None)
+
+
+def parse_compact_flag(req) -> bool:
+    """The optional "compact" field of POST /pods/remove; ValueError if it
+    is there and not a boolean."""
+    compact = req.get("compact", False)
+    if not isinstance(compact, bool):
+        raise ValueError("field 'compact' must be a boolean")
+    return compact
+
+
+def parse_compact_request(raw: bytes) -> None:
+    """Body of POST /pods/compact: empty, or an empty JSON object."""
+    if raw.strip() and json.loads(raw) != {}:
+        raise ValueError("empty body or {} expected")
 
 
 def make_handler(indexer: Indexer, coalescer=None):
@@ -104,6 +128,8 @@ def make_handler(indexer: Indexer, coalescer=None):
                     self._score_chat_completions()
                 elif self.path in ("/pods/clear", "/pods/remove"):
                     self._pods_purge(remove=self.path == "/pods/remove")
+                elif self.path == "/pods/compact":
+                    self._pods_compact()
                 else:
                     self._send_error(404, "not found")
             except json.JSONDecodeError:
@@ -153,14 +179,25 @@ def make_handler(indexer: Indexer, coalescer=None):
             req = self._read_json()
             try:
                 pods, model = parse_pods_request(req)
+                compact = parse_compact_flag(req) if remove else False
             except ValueError as e:
                 self._send_error(400, str(e))
                 return
             if remove:
-                out = indexer.remove_pods(pods)
+                out = (indexer.remove_pods(pods, compact=True) if compact
+                       else indexer.remove_pods(pods))
             else:
                 out = indexer.clear_pods(pods, model)
             self._send_json(200, out)
+
+        def _pods_compact(self):
+            length = int(self.headers.get("Content-Length", 0))
+            try:
+                parse_compact_request(self.rfile.read(length))
+            except ValueError as e:  # JSONDecodeError is one
+                self._send_error(400, str(e))
+                return
+            self._send_json(200, indexer.compact_pod_ids())
 
         def _score_chat_completions(self):
             req = self._read_json()

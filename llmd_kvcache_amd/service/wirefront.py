@@ -115,13 +115,16 @@ class WireIndexerService:
 
     def _score_tokens_cb(self, model: str, pods: Sequence[str],
                          tokens_flat, offsets):
-        (idx, model_id, filt, weights, num_pods, n_tiers, init,
-         bs) = self._stage(model, pods)
-        scores = self._run_flat(
-            idx, *idx.table._t(), tokens_flat, offsets, model_id, filt,
-            weights, num_pods, idx.table.next_epoch(), init, bs, n_tiers,
-            self._algo_id, self._device_chain(idx, offsets, bs))
-        return scores, list(idx.registry.id_to_pod)
+        # pod ids stand still from staging to naming: wire_score_flat
+        # returns host scores, so nothing id-ordered outlives the span
+        with self.indexer.kv_block_index().registry.ids_shared():
+            (idx, model_id, filt, weights, num_pods, n_tiers, init,
+             bs) = self._stage(model, pods)
+            scores = self._run_flat(
+                idx, *idx.table._t(), tokens_flat, offsets, model_id, filt,
+                weights, num_pods, idx.table.next_epoch(), init, bs, n_tiers,
+                self._algo_id, self._device_chain(idx, offsets, bs))
+            return scores, list(idx.registry.id_to_pod)
 
     def _score_text_cb(self, model: str, pods: Sequence[str],
                        prompts: List[str]):
@@ -133,13 +136,14 @@ class WireIndexerService:
         else:  # custom pool injected without the batch API
             token_lists = [pool.tokenize(None, p, model) for p in prompts]
         flat_t, off_t = pack_token_lists(token_lists)
-        (idx, model_id, filt, weights, num_pods, n_tiers, init,
-         bs) = self._stage(model, pods)
-        scores = self._run_flat(
-            idx, *idx.table._t(), flat_t, off_t, model_id, filt, weights,
-            num_pods, idx.table.next_epoch(), init, bs, n_tiers,
-            self._algo_id, self._device_chain(idx, off_t, bs))
+        with self.indexer.kv_block_index().registry.ids_shared():
+            (idx, model_id, filt, weights, num_pods, n_tiers, init,
+             bs) = self._stage(model, pods)
+            scores = self._run_flat(
+                idx, *idx.table._t(), flat_t, off_t, model_id, filt, weights,
+                num_pods, idx.table.next_epoch(), init, bs, n_tiers,
+                self._algo_id, self._device_chain(idx, off_t, bs))
+            names = list(idx.registry.id_to_pod)
         # 4-tuple: the C++ side feeds elements 2/3 (int32 tokens +
         # offsets) into its prompt cache so repeats skip Python
-        return (scores, list(idx.registry.id_to_pod),
-                flat_t.to(torch.int32), off_t)
+        return (scores, names, flat_t.to(torch.int32), off_t)
