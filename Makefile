@@ -54,3 +54,6 @@ asan:
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=all -o build/remap_asan_check \
 	    scripts/remap_asan_check.cc && ./build/remap_asan_check
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	    -fno-sanitize-recover=all -o build/census_asan_check \
+	    scripts/census_asan_check.cc && ./build/census_asan_check

@@ -183,6 +183,15 @@ class Indexer:
         dense ids return zeros and num_pods None."""
         return self._kv_block_index.compact_pod_ids()
 
+    def pod_census(self, model_name: Optional[str] = None
+                   ) -> Dict[str, object]:
+        """What the index holds, per pod and tier, and how full its tables
+        are (Index.pod_census has the layout): one read-only sweep on
+        table-backed indexes.  Nothing acts on it; it is the measurement
+        for deciding when to call remove_pods, compact_pod_ids or the
+        table's compact().  Raises NotImplementedError on Redis/Valkey."""
+        return self._kv_block_index.pod_census(model_name)
+
     def _ids_shared(self):
         """The index registry's shared id gate (pod ids do not change
         inside), or a no-op on backends without dense ids."""

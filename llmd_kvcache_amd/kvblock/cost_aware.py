@@ -191,6 +191,13 @@ class CostAwareMemoryIndex(Index):
         return {"entries_cleared": entries_cleared,
                 "keys_tombstoned": keys_dropped, "pods": sorted(seen)}
 
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        with self._mu:
+            return self._census_of_entries(
+                model_name,
+                [list(entries) for key, entries in self._data.items()
+                 if model_name is None or key.model_name == model_name])
+
     def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
         out = self.clear_pods(pods, None)
         if compact:

@@ -328,6 +328,18 @@ class KvTable:
         moved, cleared, keys = fn(*self._t(), t.contiguous())
         return int(moved), int(cleared), int(keys)
 
+    def pod_census(self, model_id: int = -1, num_pods: int = MAX_PODS,
+                   n_tiers: int = MAX_TIERS):
+        """Read-only count over meta, pods and e_meta (model_id -1: every
+        model).  Returns host tensors (counts int64 [num_pods, n_tiers],
+        summary int64 [6]: keys_live, keys_tombstoned, keys_full, entries,
+        entries_unknown, emap_occupied); see kvidx_common.h for what each
+        counts.  On a GPU table one sweep on the current stream."""
+        fn = (self.ops.gpu_pod_census if self.is_cuda
+              else self.ops.cpu_pod_census)
+        counts, summary = fn(*self._t(), model_id, num_pods, n_tiers)
+        return counts, summary
+
     def lookup(self, request_hashes, model_id, filter_words, num_pods,
                sharded=True, n_tiers=MAX_TIERS):
         fn = self.ops.gpu_lookup if self.is_cuda else self.ops.cpu_lookup
@@ -664,6 +676,46 @@ class TableIndex(Index):
         afterwards; registry.pod_generation tells."""
         with self.registry.ids_exclusive(), self._write_lock:
             return self._compact_locked([self])
+
+    # -- pod census ----------------------------------------------------
+    CENSUS_TABLE_FIELDS = ("keys_live", "keys_tombstoned", "keys_full",
+                           "entries", "entries_unknown", "emap_occupied")
+
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        """One read-only sweep over the table, on its device.  The id gate
+        is held shared from the launch until the ids are names again, so a
+        concurrent compact_pod_ids cannot renumber under it; no write lock
+        is taken (advisory, like a read).  A model nobody stored under
+        gives zeros and is not registered.  Entries of a released pod id
+        count as unknown."""
+        reg = self.registry
+        with reg.ids_shared():
+            pod_names = list(reg.id_to_pod)  # "" = released id
+            tier_names = list(reg.id_to_tier)
+            out = {"model": model_name, "entries_unknown": 0,
+                   "pods": {p: {t: 0 for t in tier_names}
+                            for p in pod_names if p}}
+            table = {"capacity": self.table.keys.numel(),
+                     **{f: 0 for f in self.CENSUS_TABLE_FIELDS
+                        if f != "entries_unknown"}}
+            out["tables"] = [table]
+            model_id = -1
+            if model_name is not None:
+                model_id = reg.model_to_id.get(model_name)
+                if model_id is None:
+                    return out
+            counts, summary = self.table.pod_census(
+                model_id, max(1, len(pod_names)), max(1, len(tier_names)))
+            summary = dict(zip(self.CENSUS_TABLE_FIELDS, summary.tolist()))
+            unknown = summary.pop("entries_unknown")
+            for pid, row in enumerate(counts.tolist()[:len(pod_names)]):
+                if pod_names[pid]:
+                    out["pods"][pod_names[pid]] = dict(zip(tier_names, row))
+                else:
+                    unknown += sum(row)
+            out["entries_unknown"] = unknown
+            table.update(summary)
+            return out
 
     # -- fast paths ----------------------------------------------------
     def fused_scores(self, hashes: torch.Tensor, counts_or_offsets: torch.Tensor,

@@ -165,6 +165,19 @@ class InMemoryIndex(Index):
         return {"entries_cleared": entries_cleared,
                 "keys_tombstoned": keys_dropped, "pods": sorted(seen)}
 
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        """Counted in Python over a snapshot of the key LRU (recency is
+        left alone), each pod cache under its own lock."""
+        def entry_lists():
+            for key in self._data.keys():
+                if model_name is not None and key.model_name != model_name:
+                    continue
+                pod_cache, found = self._data.peek(key)
+                if found and pod_cache is not None:
+                    with pod_cache.mu:
+                        yield list(pod_cache.cache.keys())
+        return self._census_of_entries(model_name, entry_lists())
+
     def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
         """No id space to give back (or to compact) here: the same as
         clear_pods for all models."""

@@ -77,6 +77,48 @@ class Index:
         nothing to renumber: zeros, and num_pods None."""
         return dict(self.NO_DENSE_IDS)
 
+    # -- pod census -----------------------------------------------------
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        """What the index holds, for one model or (None) for all:
+
+            {"model": name or None,
+             "pods": {pod_name: {tier_name: blocks}},
+             "entries_unknown": int,
+             "tables": [{"capacity", "keys_live", "keys_tombstoned",
+                         "keys_full", "entries", "emap_occupied"}]}
+
+        "pods" lists every pod the backend knows, those that hold nothing
+        included (table-backed indexes: every registered pod, with every
+        registered tier).  "entries_unknown" counts entries whose pod or
+        tier the registry cannot name.  "tables" has one item per native
+        table and is empty for backends without one.  Advisory, like a
+        read: concurrent writers are not held off.  Read-only; backends
+        that cannot enumerate their keys raise NotImplementedError."""
+        raise NotImplementedError(
+            f"{type(self).__name__} cannot take a pod census")
+
+    @staticmethod
+    def _census_of_entries(model_name: Optional[str], entry_lists) -> dict:
+        """pod_census() result for a backend that keys entries by name."""
+        pods: dict = {}
+        for entries in entry_lists:
+            for e in entries:
+                tiers = pods.setdefault(e.pod_identifier, {})
+                tiers[e.device_tier] = tiers.get(e.device_tier, 0) + 1
+        return {"model": model_name, "pods": pods, "entries_unknown": 0,
+                "tables": []}
+
+    @staticmethod
+    def _merge_census_pods(results) -> dict:
+        """Sum of the "pods" dicts of several census results."""
+        pods: dict = {}
+        for r in results:
+            for pod, tiers in r["pods"].items():
+                mine = pods.setdefault(pod, {})
+                for tier, n in tiers.items():
+                    mine[tier] = mine.get(tier, 0) + n
+        return pods
+
 
 @dataclass
 class IndexConfig:

@@ -130,5 +130,8 @@ class InstrumentedIndex(Index):
     def compact_pod_ids(self) -> dict:
         return self._count_purge(self.inner.compact_pod_ids())
 
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        return self.inner.pod_census(model_name)
+
     def __getattr__(self, name):
         return getattr(self.inner, name)

@@ -224,6 +224,13 @@ class RedisIndex(Index):
     def retire_pods(self, pods: Sequence[str], compact: bool = False) -> dict:
         raise NotImplementedError(self._PURGE_MSG)
 
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        # the same full-keyspace scan, only reading
+        raise NotImplementedError(
+            "pod census is not implemented for the Redis/Valkey backend: it "
+            "needs a full-keyspace scan of a shared server, which is left "
+            "to the operator")
+
 
 class ValkeyIndex(RedisIndex):
     backend_name = "valkey"

@@ -119,6 +119,17 @@ class TieredIndex(Index):
         return self._merge_purge([self.hot.clear_pods(pods, model_name),
                                   self.cold.clear_pods(pods, model_name)])
 
+    def pod_census(self, model_name: Optional[str] = None) -> dict:
+        """Both tiers counted and summed per pod and tier name; "tables"
+        lists the hot tier's tables, then the cold tier's.  A block held
+        in both tiers counts in both."""
+        outs = [self.hot.pod_census(model_name),
+                self.cold.pod_census(model_name)]
+        return {"model": model_name,
+                "pods": self._merge_census_pods(outs),
+                "entries_unknown": sum(o["entries_unknown"] for o in outs),
+                "tables": [t for o in outs for t in o["tables"]]}
+
     def _table_tiers(self):
         """(hot, cold) when both are tables on one registry, else None."""
         from .gpu_index import TableIndex

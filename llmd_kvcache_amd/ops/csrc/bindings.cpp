@@ -26,6 +26,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cpu_evict", &kvidx::cpu_evict);
   m.def("cpu_purge_pods", &kvidx::cpu_purge_pods);
   m.def("cpu_remap_pods", &kvidx::cpu_remap_pods);
+  m.def("cpu_pod_census", &kvidx::cpu_pod_census);
   m.def("cpu_lookup", &kvidx::cpu_lookup);
   m.def("cpu_fused_score", &kvidx::cpu_fused_score);
   m.def("cpu_score_from_masks", &kvidx::cpu_score_from_masks);
@@ -39,6 +40,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_purge_pods", &kvidx::gpu_purge_pods,
         py::call_guard<py::gil_scoped_release>());
   m.def("gpu_remap_pods", &kvidx::gpu_remap_pods,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("gpu_pod_census", &kvidx::gpu_pod_census,
         py::call_guard<py::gil_scoped_release>());
   m.def("gpu_get_request_keys", &kvidx::gpu_get_request_keys);
   m.def("gpu_lookup", &kvidx::gpu_lookup);

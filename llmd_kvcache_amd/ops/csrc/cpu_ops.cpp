@@ -394,6 +394,21 @@ std::vector<int64_t> kvidx::cpu_remap_pods(KVIDX_TABLE_PARAMS,
   return {c.entries_moved, c.entries_cleared, c.keys_tombstoned};
 }
 
+// Pod census: the sweep is pod_census_host (kvidx_common.h, torch-free).
+std::vector<at::Tensor> kvidx::cpu_pod_census(KVIDX_TABLE_PARAMS,
+                                              int64_t model_id,
+                                              int64_t num_pods,
+                                              int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, false);
+  census_bins_checked(KVIDX_TABLE_ARGS, model_id, num_pods, n_tiers);
+  auto counts = at::empty({num_pods, n_tiers}, keys.options().dtype(at::kLong));
+  auto summary = at::empty({CENSUS_SUMMARY_LEN}, counts.options());
+  pod_census_host(v, model_id, (int)num_pods, (int)n_tiers,
+                  counts.data_ptr<int64_t>(),
+                  reinterpret_cast<CensusSummary*>(summary.data_ptr<int64_t>()));
+  return {counts, summary};
+}
+
 // found: 0 absent, 1 present-with-visible-pods, 2 present-but-empty
 // (chain-cut marker, in_memory.go:118-121).
 std::vector<at::Tensor> kvidx::cpu_lookup(KVIDX_TABLE_PARAMS,

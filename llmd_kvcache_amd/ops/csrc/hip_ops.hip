@@ -614,6 +614,215 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
   }
 }
 
+// ---- pod census --------------------------------------------------------
+// The third sweep of the family, and the read-only one: the purge's tiles
+// of PURGE_ROWS whole rows and its 16-byte loads, four in flight per lane,
+// but nothing goes back to the table.  What it keeps instead:
+//  - the pod x tier histogram, uint32 bins in dynamic LDS (num_pods *
+//    n_tiers words: 512 B for 64 pods x 2 tiers, 64 KB at MAX_PODS x
+//    MAX_TIERS), zeroed once per workgroup and carried across its
+//    grid-stride loop; a non-empty entry of a live row is one ds_add_u32
+//    with no return value;
+//  - one LDS word per tile row: the row's meta bits (OCC, TOMB, model) with
+//    a count of the row's non-zero entries in the free bits 16..29.  A lane
+//    sums the non-zero entries it saw of a row over its vector and adds
+//    them there once; after the barrier thread r classifies row r from
+//    that one word (live / tombstoned / full) and looks at e_meta[row0 +
+//    r], whose load went out with the meta load;
+//  - unknown-bin hits and the six scalar counters in registers.
+// Each workgroup leaves through plain stores into its row of partials
+// [gridDim.x][bins + 6]; k_census_reduce sums the rows.  No fill pass, no
+// global atomic, and no dword of the table is read twice.
+constexpr uint32_t ROW_COUNT_SHIFT = 16;  // pods_per_key <= 4096: 13 bits
+constexpr uint32_t ROW_META_BITS = META_OCC | META_TOMB | META_MODEL_MASK;
+constexpr uint32_t ROW_COUNT_MASK = 0x3FFFu;
+constexpr int64_t CENSUS_PARTIAL_BYTES = 32ll << 20;
+
+// One entry e (possibly empty) of a tile row whose LDS word is rw.  The
+// counters move by predicates; the one branch is around the LDS add.
+DEV void census_entry(uint32_t e, uint32_t rw, int model_id,
+                      uint32_t num_pods, uint32_t n_tiers, uint32_t* s_hist,
+                      uint32_t& n_entries, uint32_t& n_unknown) {
+  const bool counted = e != 0 && census_slot(rw, model_id) == CENSUS_LIVE;
+  const int32_t b = census_bin(e, num_pods, n_tiers);
+  n_entries += counted ? 1u : 0u;
+  n_unknown += (counted && b < 0) ? 1u : 0u;
+  if (counted && b >= 0)
+    atomicAdd(&s_hist[b], 1u);  // result unused: no return value asked for
+}
+
+// A table of fewer than 4 rows (capacity 1 or 2) can have fewer than 4
+// dwords, or a dword count that is no multiple of 4: one workgroup walks
+// it dword by dword.  Every larger table is whole vectors.
+DEV void census_tiny_table(const Table& v, int model_id, uint32_t num_pods,
+                           uint32_t n_tiers, uint32_t* s_hist, uint32_t* s_row,
+                           uint32_t& n_entries, uint32_t& n_unknown) {
+  const uint32_t P = (uint32_t)v.pods_per_key;
+  const uint32_t rows = (uint32_t)v.cap_mask + 1;
+  if (threadIdx.x < rows) s_row[threadIdx.x] = v.meta[threadIdx.x] & ROW_META_BITS;
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < rows * P; i += PURGE_THREADS) {
+    const uint32_t e = v.pods[i];
+    census_entry(e, s_row[i / P], model_id, num_pods, n_tiers, s_hist,
+                 n_entries, n_unknown);
+    if (e != 0) atomicAdd(&s_row[i / P], 1u << ROW_COUNT_SHIFT);
+  }
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(PURGE_THREADS) k_pod_census(
+    Table v, int model_id, int num_pods, int n_tiers, int64_t n_tiles,
+    uint32_t* __restrict__ partials) {
+  extern __shared__ uint32_t s_hist[];  // [num_pods * n_tiers]
+  __shared__ uint32_t s_row[PURGE_ROWS];
+  __shared__ uint32_t s_red[CENSUS_SUMMARY_LEN * (PURGE_THREADS / 64)];
+  const int tid = threadIdx.x;
+  const uint32_t P = (uint32_t)v.pods_per_key;
+  const uint64_t cap = v.cap_mask + 1;
+  const uint32_t un_pods = (uint32_t)num_pods, un_tiers = (uint32_t)n_tiers;
+  const uint32_t bins = un_pods * un_tiers;
+  for (uint32_t i = tid; i < bins; i += PURGE_THREADS) s_hist[i] = 0;
+  // (the first tile's barrier publishes the zeros)
+  uint32_t n_live = 0, n_tomb = 0, n_full = 0, n_entries = 0, n_unknown = 0,
+           n_emap = 0;
+
+  // thread r owns row r: its word in s_row, and the engine-map word em
+  auto classify = [&](int rows, uint32_t em) {
+    if (tid >= rows) return;
+    const uint32_t rw = s_row[tid];
+    const CensusSlot c = census_slot(rw, model_id);
+    n_live += c == CENSUS_LIVE;
+    n_tomb += c == CENSUS_TOMB;
+    n_full += c == CENSUS_LIVE &&
+              ((rw >> ROW_COUNT_SHIFT) & ROW_COUNT_MASK) == P;
+    n_emap += census_slot(em, model_id) == CENSUS_LIVE;
+  };
+
+  if (cap < 4) {  // one tile, one workgroup (the op launches one)
+    if (blockIdx.x == 0) {
+      census_tiny_table(v, model_id, un_pods, un_tiers, s_hist, s_row,
+                        n_entries, n_unknown);
+      classify((int)cap, (uint64_t)tid < cap ? v.e_meta[tid] : 0u);
+    }
+    n_tiles = 0;
+  }
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    // capacity >= 4: a tile is 4..256 rows, a whole number of vectors
+    const uint64_t row0 = (uint64_t)tile * PURGE_ROWS;
+    const uint64_t rows_left = cap - row0;
+    const int rows = rows_left < PURGE_ROWS ? (int)rows_left : PURGE_ROWS;
+    const uint32_t n_vec = ((uint32_t)rows * P) >> 2;
+    const uint4* tile_v = reinterpret_cast<const uint4*>(v.pods + row0 * P);
+
+    // Every load is unconditional, at a clamped index, so that all of a
+    // round's loads go out back to back and each is waited for by its own
+    // count: meta first (the only one needed ahead of the barrier), e_meta
+    // right behind it (not looked at until the tile is done), then the
+    // vectors.  A lane past the end rereads the last row or vector, a
+    // line its neighbours fetch anyway, and drops it.
+    const uint64_t my_row = row0 + (uint32_t)(tid < rows ? tid : rows - 1);
+    const uint32_t m_mine = v.meta[my_row];
+    const uint32_t em_mine = v.e_meta[my_row];
+    uint32_t base = 0;
+    do {
+      uint4 q[PURGE_VECS];
+#pragma unroll
+      for (int k = 0; k < PURGE_VECS; ++k) {
+        const uint32_t vi = base + k * PURGE_THREADS + tid;
+        q[k] = tile_v[vi < n_vec ? vi : n_vec - 1];
+      }
+      if (base == 0) {
+        s_row[tid] = tid < rows ? (m_mine & ROW_META_BITS) : 0u;
+        __syncthreads();
+      }
+#pragma unroll
+      for (int k = 0; k < PURGE_VECS; ++k) {
+        const uint32_t vi = base + k * PURGE_THREADS + tid;
+        if (vi >= n_vec || (q[k].x | q[k].y | q[k].z | q[k].w) == 0) continue;
+        const uint32_t i0 = vi * 4;
+        const uint32_t e[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+        // the tile row of each of the four dwords (all inside the tile),
+        // then the four row words in one round of LDS reads
+        uint32_t r[4];
+        r[0] = i0 / P;
+        uint32_t col = i0 - r[0] * P;
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+          const bool wrap = ++col == P;
+          col = wrap ? 0u : col;
+          r[j] = r[j - 1] + (wrap ? 1u : 0u);
+        }
+        uint32_t rw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rw[j] = s_row[r[j]];
+        uint32_t run = 0;  // non-zero entries of the current row so far
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          census_entry(e[j], rw[j], model_id, un_pods, un_tiers, s_hist,
+                       n_entries, n_unknown);
+          run += e[j] != 0 ? 1u : 0u;
+          if (j == 3 || r[j + 1 < 4 ? j + 1 : 3] != r[j]) {
+            if (run) atomicAdd(&s_row[r[j]], run << ROW_COUNT_SHIFT);
+            run = 0;
+          }
+        }
+      }
+      base += PURGE_THREADS * PURGE_VECS;
+    } while (base < n_vec);
+    __syncthreads();
+    // thread r rewrites row r's word itself for the next tile, so no
+    // third barrier
+    classify(rows, em_mine);
+  }
+
+  // counters: wave, then workgroup; the barrier also closes the histogram
+  uint32_t c[CENSUS_SUMMARY_LEN] = {n_live,    n_tomb,    n_full,
+                                    n_entries, n_unknown, n_emap};
+#pragma unroll
+  for (int i = 0; i < CENSUS_SUMMARY_LEN; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c[i] += __shfl_down(c[i], off, 64);
+    if ((tid & 63) == 0) s_red[CENSUS_SUMMARY_LEN * (tid >> 6) + i] = c[i];
+  }
+  __syncthreads();
+  uint32_t* mine = partials + (size_t)blockIdx.x * (bins + CENSUS_SUMMARY_LEN);
+  for (uint32_t i = tid; i < bins; i += PURGE_THREADS) mine[i] = s_hist[i];
+  if (tid < CENSUS_SUMMARY_LEN) {
+    uint32_t s = 0;
+    for (int w = 0; w < PURGE_THREADS / 64; ++w)
+      s += s_red[CENSUS_SUMMARY_LEN * w + tid];
+    mine[bins + tid] = s;
+  }
+}
+
+// out[c] = sum over the n_rows workgroup rows of partials[r][c].  A thread
+// owns one column, so the 64 lanes of a wave read 64 neighbouring words of
+// a row; with one thread per column and nothing else, 134 columns under
+// 2048 rows were one workgroup walking 2048 dependent loads (0.46 ms
+// measured), so a workgroup is 64 columns x 16 row slices: wave s sums rows
+// s, s + 16, ... of its columns, eight loads in flight, and the slices meet
+// in LDS.
+constexpr int REDUCE_COLS = 64, REDUCE_SLICES = 16;
+__global__ void __launch_bounds__(REDUCE_COLS * REDUCE_SLICES)
+    k_census_reduce(const uint32_t* __restrict__ partials, int n_rows,
+                    int n_cols, int64_t* __restrict__ out) {
+  __shared__ unsigned long long s_part[REDUCE_SLICES][REDUCE_COLS];
+  const int lane = threadIdx.x % REDUCE_COLS, slice = threadIdx.x / REDUCE_COLS;
+  const int c = blockIdx.x * REDUCE_COLS + lane;
+  unsigned long long s = 0;
+  if (c < n_cols) {
+#pragma unroll 8
+    for (int r = slice; r < n_rows; r += REDUCE_SLICES)
+      s += partials[(size_t)r * n_cols + c];
+  }
+  s_part[slice][lane] = s;
+  __syncthreads();
+  if (slice == 0 && c < n_cols) {
+    for (int i = 1; i < REDUCE_SLICES; ++i) s += s_part[i][lane];
+    out[c] = (int64_t)s;
+  }
+}
+
 __global__ void k_get_request_keys(Table v,
                                    const uint64_t* __restrict__ eh, int64_t n,
                                    uint32_t model, uint8_t* __restrict__ found,
@@ -1588,6 +1797,52 @@ std::vector<int64_t> kvidx::gpu_remap_pods(KVIDX_TABLE_PARAMS,
     tombs += hp[3 * b + 2];
   }
   return {moved, cleared, tombs};
+}
+
+// The sweep, the reduce and one readback of bins + 6 int64 words, on the
+// current stream.  The grid is capped so that the partials stay within
+// CENSUS_PARTIAL_BYTES: 511 workgroups at 16384 bins, which is also what 2
+// workgroups of 64 KB LDS per CU come to.
+std::vector<at::Tensor> kvidx::gpu_pod_census(KVIDX_TABLE_PARAMS,
+                                              int64_t model_id,
+                                              int64_t num_pods,
+                                              int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  const int64_t bins =
+      census_bins_checked(KVIDX_TABLE_ARGS, model_id, num_pods, n_tiers);
+  TORCH_CHECK(meta.device() == keys.device() &&
+                  pods.device() == keys.device() &&
+                  e_meta.device() == keys.device(),
+              "table tensors must share one device");
+  // tiles are read as 16-byte vectors from the start of the array
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
+              "pods storage must be 16-byte aligned");
+  const int64_t cap = keys.numel();
+  const int64_t cols = bins + CENSUS_SUMMARY_LEN;
+  const int64_t n_tiles = (cap + PURGE_ROWS - 1) / PURGE_ROWS;
+  const int64_t grid = std::max<int64_t>(
+      1, std::min<int64_t>({n_tiles, (int64_t)PURGE_MAX_BLOCKS,
+                            CENSUS_PARTIAL_BYTES / (4 * cols)}));
+  // a workgroup's uint32 bins and counters cannot wrap
+  const int64_t tiles_per_wg = (n_tiles + grid - 1) / grid;
+  TORCH_CHECK(tiles_per_wg * PURGE_ROWS * pods_per_key < (1ll << 32),
+              "table too large for 32-bit per-workgroup census counters");
+  auto partials = at::empty({grid, cols}, keys.options().dtype(at::kInt));
+  auto sums = at::empty({cols}, keys.options().dtype(at::kLong));
+  hipLaunchKernelGGL(k_pod_census, dim3((unsigned)grid), dim3(PURGE_THREADS),
+                     (size_t)bins * sizeof(uint32_t), STREAM, v, (int)model_id,
+                     (int)num_pods, (int)n_tiers, n_tiles, u32p(partials));
+  hipLaunchKernelGGL(k_census_reduce,
+                     dim3((unsigned)((cols + REDUCE_COLS - 1) / REDUCE_COLS)),
+                     dim3(REDUCE_COLS * REDUCE_SLICES), 0, STREAM,
+                     u32p(partials), (int)grid, (int)cols,
+                     sums.data_ptr<int64_t>());
+  auto err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "pod census launch failed: ",
+              hipGetErrorString(err));
+  auto host = sums.cpu();  // waits for both kernels
+  return {host.narrow(0, 0, bins).view({num_pods, n_tiers}),
+          host.narrow(0, bins, CENSUS_SUMMARY_LEN)};
 }
 
 std::vector<at::Tensor> kvidx::gpu_get_request_keys(

@@ -696,6 +696,70 @@ inline RemapCounts remap_pods_host(const Table& v, const int32_t* remap,
   return out;
 }
 
+// ---- pod census -------------------------------------------------------
+// A read-only count of what the table holds, for one model or for all
+// (model_id -1).  These definitions are the host sweep's and
+// k_pod_census's alike.
+//
+// A slot (main table or engine map) is LIVE if OCC is set, TOMB is clear
+// and its model matches; TOMBSTONED if OCC and TOMB are set and the model
+// matches; anything else takes no part.
+enum CensusSlot : int { CENSUS_NONE = 0, CENSUS_LIVE = 1, CENSUS_TOMB = 2 };
+KVIDX_HD CensusSlot census_slot(uint32_t m, int64_t model_id) {
+  if (!purge_slot_eligible(m, model_id)) return CENSUS_NONE;
+  return (m & META_TOMB) ? CENSUS_TOMB : CENSUS_LIVE;
+}
+// Histogram bin pid * n_tiers + tier of a non-zero entry, or -1 where the
+// id or the tier lies past what the registry knows: the bin index is
+// bounded here, and the out-of-range entry becomes a count of its own.
+KVIDX_HD int32_t census_bin(uint32_t e, uint32_t num_pods, uint32_t n_tiers) {
+  const uint32_t pid = pod_entry_id(e);
+  const uint32_t tier = pod_entry_tier(e);
+  return (pid < num_pods && tier < n_tiers) ? (int32_t)(pid * n_tiers + tier)
+                                            : -1;
+}
+
+// Order of the ops' summary tensor.
+struct CensusSummary {
+  int64_t keys_live = 0;        // live slots
+  int64_t keys_tombstoned = 0;  // tombstoned slots
+  int64_t keys_full = 0;        // live slots with no zero entry
+  int64_t entries = 0;          // non-zero entries in live slots
+  int64_t entries_unknown = 0;  // ... of those, the ones census_bin rejects
+  int64_t emap_occupied = 0;    // live engine-map slots
+};
+static constexpr int CENSUS_SUMMARY_LEN = 6;
+static_assert(sizeof(CensusSummary) == CENSUS_SUMMARY_LEN * sizeof(int64_t),
+              "the summary is read as int64 [6]");
+
+// Host sweep: counts[num_pods * n_tiers] (row-major pod, tier) and *sum
+// are overwritten.  Entries of tombstoned or unoccupied slots are never
+// counted.  Reads meta, pods and e_meta only; k_pod_census is the device
+// twin.
+inline void pod_census_host(const Table& v, int64_t model_id, int num_pods,
+                            int n_tiers, int64_t* counts, CensusSummary* sum) {
+  for (int i = 0; i < num_pods * n_tiers; ++i) counts[i] = 0;
+  CensusSummary s;
+  for (uint64_t i = 0; i <= v.cap_mask; ++i) {
+    s.emap_occupied += census_slot(v.e_meta[i], model_id) == CENSUS_LIVE;
+    const CensusSlot c = census_slot(v.meta[i], model_id);
+    s.keys_tombstoned += c == CENSUS_TOMB;
+    if (c != CENSUS_LIVE) continue;
+    ++s.keys_live;
+    const uint32_t* p = v.pods + i * (uint64_t)v.pods_per_key;
+    int nz = 0;
+    for (int k = 0; k < v.pods_per_key; ++k) {
+      if (p[k] == 0) continue;
+      ++nz;
+      const int32_t b = census_bin(p[k], (uint32_t)num_pods, (uint32_t)n_tiers);
+      if (b >= 0) ++counts[b]; else ++s.entries_unknown;
+    }
+    s.entries += nz;
+    s.keys_full += nz == v.pods_per_key;
+  }
+  *sum = s;
+}
+
 // Sharding: the main table holds only the keys a shard owns (the engine
 // map is replicated on every shard).
 KVIDX_HD bool owns_key(uint64_t h, int shard_id, int num_shards) {

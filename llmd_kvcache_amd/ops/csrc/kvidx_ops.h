@@ -61,6 +61,13 @@ std::vector<int64_t> cpu_purge_pods(KVIDX_TABLE_PARAMS, at::Tensor purge_words,
 // by a compare-and-swap the way a raced purge can, so the sweeps use plain
 // stores.
 std::vector<int64_t> cpu_remap_pods(KVIDX_TABLE_PARAMS, at::Tensor remap);
+// Pod census (definitions: kvidx_common.h): read-only; model_id -1 = every
+// model, 1 <= num_pods <= MAX_PODS, 1 <= n_tiers <= MAX_TIERS.
+// -> {counts int64 [num_pods, n_tiers], summary int64 [6] in CensusSummary
+// order}, both on the host.  Advisory under concurrent writers: every word
+// is read once, a row's meta and entries possibly at different instants.
+std::vector<at::Tensor> cpu_pod_census(KVIDX_TABLE_PARAMS, int64_t model_id,
+                                       int64_t num_pods, int64_t n_tiers);
 std::vector<at::Tensor> cpu_lookup(KVIDX_TABLE_PARAMS,
                                    at::Tensor request_hashes, int64_t model_id,
                                    at::Tensor filter_words, int64_t num_pods,
@@ -91,6 +98,9 @@ std::vector<int64_t> gpu_purge_pods(KVIDX_TABLE_PARAMS, at::Tensor purge_words,
                                     int64_t model_id);
 // remap on the table's device; the sweep has completed on return
 std::vector<int64_t> gpu_remap_pods(KVIDX_TABLE_PARAMS, at::Tensor remap);
+// one sweep and one small reduce on the current stream, one readback
+std::vector<at::Tensor> gpu_pod_census(KVIDX_TABLE_PARAMS, int64_t model_id,
+                                       int64_t num_pods, int64_t n_tiers);
 std::vector<at::Tensor> gpu_get_request_keys(KVIDX_TABLE_PARAMS,
                                              at::Tensor engine_hashes,
                                              int64_t model_id);
@@ -233,6 +243,24 @@ inline int remap_checked(const at::Tensor& remap) {
     taken[r[i]] = 1;
   }
   return (int)n;
+}
+
+// Histogram bins of a census, after the checks both census ops share.
+inline int64_t census_bins_checked(KVIDX_TABLE_PARAMS, int64_t model_id,
+                                   int64_t num_pods, int64_t n_tiers) {
+  TORCH_CHECK(num_pods >= 1 && num_pods <= MAX_PODS, "num_pods must be 1..",
+              MAX_PODS);
+  TORCH_CHECK(n_tiers >= 1 && n_tiers <= MAX_TIERS, "n_tiers must be 1..",
+              MAX_TIERS);
+  TORCH_CHECK(model_id >= -1 && model_id <= (int64_t)META_MODEL_MASK,
+              "model_id out of range (-1 = every model)");
+  TORCH_CHECK(pods_per_key >= 1 && pods_per_key <= 4096,
+              "pods_per_key out of range");
+  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
+              "pods must hold capacity * pods_per_key entries");
+  TORCH_CHECK(meta.numel() == keys.numel() && e_meta.numel() == keys.numel(),
+              "meta and e_meta must hold capacity words");
+  return num_pods * n_tiers;
 }
 
 // Runs f(std::integral_constant<int, ALGO>) for a native chain algo id

@@ -16,6 +16,7 @@ Protocol (collective ops driven by rank 0):
   ("score", hashes_i64_list, offsets, model, pods) score collectively
   ("retire", pods)                                 purge + release ids
   ("clear", pods, model)                           purge, ids kept
+  ("census", model)                                count, gather to rank 0
   ("stop",)                                        exit serve loops
 """
 
@@ -29,7 +30,7 @@ import torch.distributed as dist
 from ..kvblock.gpu_index import _to_i64
 from ..kvblock.token_processor import ChunkedTokenDatabase
 from ..kvevents.events import decode_event_batch
-from .sharded import ShardedIndex, check_registry_sync
+from .sharded import ShardedIndex, check_registry_sync, merge_census
 
 SYNC_CHECK_INTERVAL = 64  # apply_messages calls between registry audits
 
@@ -94,6 +95,21 @@ class ShardedIndexService:
             return self.sharded.compact_pod_ids()
         if kind == "clear":
             return self.sharded.clear_pods(list(op[1]), op[2])
+        if kind == "census":
+            # every rank enters the gather exactly once, also when its own
+            # census throws (None rides in its place and rank 0 raises)
+            try:
+                mine = self.sharded.pod_census(op[1])
+            except Exception:
+                mine = None
+            replies = [None] * self.sharded.world_size if self.rank == 0 \
+                else None
+            dist.gather_object(mine, replies, dst=0, group=self.group)
+            if self.rank != 0:
+                return None
+            if any(r is None for r in replies):
+                raise RuntimeError("pod census failed on a shard")
+            return merge_census(replies)
         if kind == "sync_check":
             # ROADMAP #8: loud detection of registry divergence before it
             # can misattribute merged-mask scores
@@ -193,6 +209,15 @@ class ShardedIndexService:
         the pods keep their ids."""
         assert self.rank == 0
         op = ("clear", sorted(set(pods)), model_name)
+        self._broadcast(op)
+        return self._dispatch(op)
+
+    def pod_census(self, model_name: Optional[str] = None
+                   ) -> Dict[str, object]:
+        """Census of every shard at one point of the op order, merged into
+        fleet totals (sharded.merge_census)."""
+        assert self.rank == 0
+        op = ("census", model_name)
         self._broadcast(op)
         return self._dispatch(op)
 

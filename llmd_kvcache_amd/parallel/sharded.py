@@ -123,6 +123,11 @@ class ShardedIndex:
         order end up with the same ids; the counts are this shard's."""
         return self.local.compact_pod_ids()
 
+    def pod_census(self, model_name=None) -> dict:
+        """Census of the LOCAL shard (read-only, no collective); the
+        service gathers one per rank and merge_census adds them up."""
+        return self.local.pod_census(model_name)
+
     # -- read path -----------------------------------------------------
     def sharded_scores(
         self,
@@ -327,6 +332,30 @@ def _partition_prompts(offs_cpu: torch.Tensor, world: int) -> Tuple[int, ...]:
         bounds.append(b)
     bounds.append(B)
     return tuple(bounds)
+
+
+def merge_census(results: Sequence[dict]) -> dict:
+    """One fleet-wide pod census from the per-shard ones (a pure function).
+
+    The main table is ownership-filtered, so "pods", "entries_unknown" and
+    the per-table key and entry fields ADD UP to fleet totals.  The engine
+    map is replicated: "emap_occupied" is the maximum over the shards, and
+    "capacity" is the first shard's (every shard has its own table of
+    that size)."""
+    from ..kvblock.index import Index
+
+    results = list(results)
+    tables = []
+    for per_shard in zip(*(r["tables"] for r in results)):
+        t = {k: sum(s[k] for s in per_shard)
+             for k in ("keys_live", "keys_tombstoned", "keys_full", "entries")}
+        t["emap_occupied"] = max(s["emap_occupied"] for s in per_shard)
+        t["capacity"] = per_shard[0]["capacity"]
+        tables.append(t)
+    return {"model": results[0]["model"] if results else None,
+            "pods": Index._merge_census_pods(results),
+            "entries_unknown": sum(r["entries_unknown"] for r in results),
+            "tables": tables}
 
 
 def registry_fingerprint(registry) -> int:

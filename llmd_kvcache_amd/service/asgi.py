@@ -61,6 +61,8 @@ class AsgiIndexerApp:
                 await self._pods_purge(send, body, path == "/pods/remove")
             elif method == "POST" and path == "/pods/compact":
                 await self._pods_compact(send, await self._read_raw(receive))
+            elif method == "GET" and path == "/pods/census":
+                await self._pods_census(send, scope.get("query_string", b""))
             elif method == "GET" and path == "/health":
                 await self._json(send, 200, {"status": "ok"})
             elif method == "GET" and path == "/metrics":
@@ -170,6 +172,18 @@ class AsgiIndexerApp:
             raise _BadRequest(str(e))
         loop = asyncio.get_running_loop()
         out = await loop.run_in_executor(None, self.indexer.compact_pod_ids)
+        await self._json(send, 200, out)
+
+    async def _pods_census(self, send, query: bytes):
+        """GET /pods/census[?model=NAME]: a table sweep and a readback, so
+        off the loop."""
+        import asyncio
+
+        from .http_server import parse_census_query
+
+        model = parse_census_query(query.decode("latin-1"))
+        loop = asyncio.get_running_loop()
+        out = await loop.run_in_executor(None, self.indexer.pod_census, model)
         await self._json(send, 200, out)
 
     async def _metrics(self, send):

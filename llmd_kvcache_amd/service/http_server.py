@@ -22,6 +22,9 @@
                                   "entries_cleared", "keys_tombstoned",
                                   "num_pods", "pod_generation"}; num_pods is
                                   null on backends without dense pod ids
+ - GET  /pods/census[?model=NAME] blocks per pod and tier, entries of unknown
+                                  ids, and per-table fill (Index.pod_census);
+                                  read-only; 501 on Redis/Valkey
 
 Implemented on the stdlib http.server (threaded) to stay dependency-light
 and startable from tests; the env-config surface matches the reference
@@ -35,6 +38,7 @@ import logging
 import threading
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Optional
+from urllib.parse import parse_qs, urlsplit
 
 from ..indexer import Indexer
 from ..preprocessing import chat_completions as cc
@@ -70,6 +74,12 @@ def parse_compact_request(raw: bytes) -> None:
     """Body of POST /pods/compact: empty, or an empty JSON object."""
     if raw.strip() and json.loads(raw) != {}:
         raise ValueError("empty body or {} expected")
+
+
+def parse_census_query(query: str) -> Optional[str]:
+    """Query string of GET /pods/census -> the model name, or None (every
+    model) when there is no non-empty "model" parameter."""
+    return (parse_qs(query).get("model") or [None])[0] or None
 
 
 def make_handler(indexer: Indexer, coalescer=None):
@@ -115,6 +125,15 @@ def make_handler(indexer: Indexer, coalescer=None):
                 self.wfile.write(body)
             elif self.path == "/health":
                 self._send_json(200, {"status": "ok"})
+            elif urlsplit(self.path).path == "/pods/census":
+                try:
+                    model = parse_census_query(urlsplit(self.path).query)
+                    self._send_json(200, indexer.pod_census(model))
+                except NotImplementedError as e:
+                    self._send_error(501, str(e))
+                except Exception as e:
+                    logger.exception("request failed")
+                    self._send_error(500, f"error: {e}")
             else:
                 self._send_error(404, "not found")
 
