@@ -42,18 +42,13 @@ image:
 container-smoke:
 	BASE=$(BASE_IMAGE) IMG=$(IMAGE) bash scripts/container_smoke.sh
 
+ASAN_CHECKS = asan_check purge_asan_check remap_asan_check census_asan_check
+
 .PHONY: asan
 asan:
 	mkdir -p build
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
-	    -fno-sanitize-recover=all -o build/asan_check scripts/asan_check.cc \
-	    && ./build/asan_check
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
-	    -fno-sanitize-recover=all -o build/purge_asan_check \
-	    scripts/purge_asan_check.cc && ./build/purge_asan_check
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
-	    -fno-sanitize-recover=all -o build/remap_asan_check \
-	    scripts/remap_asan_check.cc && ./build/remap_asan_check
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
-	    -fno-sanitize-recover=all -o build/census_asan_check \
-	    scripts/census_asan_check.cc && ./build/census_asan_check
+	set -e; for c in $(ASAN_CHECKS); do \
+	    g++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	        -fno-sanitize-recover=all -o build/$$c scripts/$$c.cc; \
+	    ./build/$$c; \
+	done

@@ -346,26 +346,145 @@ __global__ void k_evict(Table v, const uint64_t* __restrict__ eh,
   dev_remove_pods(v, eh[i], model, entries, n_entries);
 }
 
+// ---- table sweeps ------------------------------------------------------
+// One pass over pods[C * P] read as the flat array it is: the shape of the
+// purge, the remap and the census.  sweep_table below walks it for the
+// purge and the census; the remap has the same walk written out (see
+// there).  A workgroup takes tiles of SWEEP_ROWS
+// whole table rows (sweep_tile in kvidx_common.h): SWEEP_ROWS * P dwords
+// start on a 1 KB boundary whatever P is, so a tile is read as 16-byte
+// vectors, consecutive lanes taking consecutive vectors, SWEEP_VECS in
+// flight per lane, and no row leaves its tile.  Inside the tile rows do
+// straddle vectors and waves (P = 10: a row is 2.5 vectors), so the lane
+// that holds a dword is not the lane that decides about its row: thread r
+// publishes row r's state in LDS under a first barrier, every lane reports
+// what it saw of a row to that state (sweep_vec_rows names the row), and
+// after a second barrier thread r reads row r's state and acts on it.
+// Nothing is read from global memory twice.
+//
+// What a kernel brings to the walk, as a struct K:
+//   row_load(row)            a per-row load that goes out with the meta load
+//   row_begin(r, m)          thread r: row r's LDS state from its meta word
+//   vec(e, r, vi, tile_p)    one loaded vector: its four dwords, their tile
+//                            rows, its index in the tile, the tile's dwords
+//   dword(e, row, p)         one dword read from *p (tables under 4 rows)
+//   row_end(r, row, x)       thread r after the second barrier; x is what
+//                            row_load returned
+// and its counters in K::c, which leave through wg_sum_store.
+
+// dst[i] = the workgroup's sum of c[i]: wave shuffle, N words per wave in
+// LDS, one barrier, N plain stores by threads 0..N-1.  Plain stores into a
+// row of per-workgroup partials, which the op sums after its readback, in
+// place of atomic adds: no counter has to be zeroed before the launch.
+template <int N>
+DEV void wg_sum_store(const uint32_t (&c)[N], uint32_t* dst) {
+  __shared__ uint32_t s_red[N * (SWEEP_THREADS / 64)];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    uint32_t x = c[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if ((tid & 63) == 0) s_red[N * (tid >> 6) + i] = x;
+  }
+  __syncthreads();
+  if (tid < N) {
+    uint32_t s = 0;
+    for (int w = 0; w < SWEEP_THREADS / 64; ++w) s += s_red[N * w + tid];
+    dst[tid] = s;
+  }
+}
+
+// A table of fewer than 4 rows (capacity 1 or 2) can have fewer than 4
+// dwords, or a dword count that is no multiple of 4: one workgroup walks
+// it dword by dword.  Every larger table is whole vectors.
+template <typename K>
+DEV void sweep_tiny_table(const Table& v, K& k) {
+  const uint32_t P = (uint32_t)v.pods_per_key;
+  const uint32_t rows = (uint32_t)v.cap_mask + 1;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t mine = tid < rows ? tid : 0u;
+  const auto x = k.row_load(mine);
+  k.row_begin((int)tid, tid < rows ? v.meta[mine] : 0u);
+  __syncthreads();
+  for (uint32_t i = tid; i < rows * P; i += SWEEP_THREADS)
+    k.dword(v.pods[i], i / P, v.pods + i);
+  __syncthreads();
+  if (tid < rows) k.row_end((int)tid, tid, x);
+}
+
+template <bool CLAMPED, typename K>
+DEV void sweep_table(const Table& v, int64_t n_tiles, K& k) {
+  const int tid = threadIdx.x;
+  const uint32_t P = (uint32_t)v.pods_per_key;
+  const uint64_t cap = v.cap_mask + 1;
+  if (cap < 4) {  // one tile, one workgroup (the op launches one)
+    if (blockIdx.x == 0) sweep_tiny_table(v, k);
+    return;
+  }
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    // capacity >= 4: a tile is 4..256 rows, a whole number of vectors
+    const SweepTile t = sweep_tile(cap, P, tile);
+    uint32_t* tile_p = v.pods + t.row0 * P;
+    const uint4* tile_v = reinterpret_cast<const uint4*>(tile_p);
+
+    // CLAMPED: every load is unconditional, at a clamped index, so that
+    // all of a round's loads go out back to back and each is waited for by
+    // its own count: meta first (the only one needed ahead of the
+    // barrier), the kernel's row load right behind it (not looked at until
+    // the tile is done), then the vectors.  A lane past the end rereads
+    // the last row or vector, a line its neighbours fetch anyway, and
+    // drops it.  Otherwise a lane past the end loads nothing and walks a
+    // zero vector.  Each kernel takes the form that measured faster for it
+    // (profiles/r10_pod_census.md, r11_table_sweeps.md).
+    const uint64_t my_row =
+        t.row0 + (uint32_t)(tid < t.rows ? tid : t.rows - 1);
+    const uint32_t m_mine =
+        CLAMPED || tid < t.rows ? v.meta[my_row] : 0u;
+    const auto x_mine = k.row_load(my_row);
+    uint32_t base = 0;
+    do {
+      uint4 q[SWEEP_VECS];
+#pragma unroll
+      for (int i = 0; i < SWEEP_VECS; ++i) {
+        const uint32_t vi = base + i * SWEEP_THREADS + tid;
+        if (CLAMPED)
+          q[i] = tile_v[vi < t.n_vec ? vi : t.n_vec - 1];
+        else
+          q[i] = vi < t.n_vec ? tile_v[vi] : make_uint4(0, 0, 0, 0);
+      }
+      if (base == 0) {
+        k.row_begin(tid, tid < t.rows ? m_mine : 0u);
+        __syncthreads();
+      }
+#pragma unroll
+      for (int i = 0; i < SWEEP_VECS; ++i) {
+        const uint32_t vi = base + i * SWEEP_THREADS + tid;
+        // a vector past the tile is dropped, not walked a second time
+        if ((CLAMPED && vi >= t.n_vec) || (q[i].x | q[i].y | q[i].z | q[i].w) == 0)
+          continue;
+        const uint32_t e[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+        uint32_t r[4];  // all inside the tile
+        sweep_vec_rows(vi, P, r);
+        k.vec(e, r, vi, tile_p);
+      }
+      base += SWEEP_THREADS * SWEEP_VECS;
+    } while (base < t.n_vec);
+    __syncthreads();
+    // thread r owns row r: it wrote the row's LDS state and is the one to
+    // rewrite it for the next tile, so no third barrier
+    if (tid < t.rows) k.row_end(tid, t.row0 + tid, x_mine);
+  }
+}
+
 // ---- purge by pod ------------------------------------------------------
-// One sweep over pods[C * P] read as the flat array it is.  A workgroup
-// takes tiles of PURGE_ROWS whole table rows: PURGE_ROWS * P dwords start
-// on a 1 KB boundary whatever P is, so a tile is read as 16-byte vectors,
-// consecutive lanes taking consecutive vectors, and no row leaves its
-// tile.  Inside the tile rows do straddle vectors and waves (P = 10: a row
-// is 2.5 vectors), so the lane that holds a dword is not the lane that
-// decides about its row: every lane reports what it saw of a row to that
-// row's flag word in LDS (ROW_HIT: cleared an entry; ROW_LIVE: an entry
-// remains), and after a barrier thread r reads row r's flags and
-// tombstones the row if it was hit and nothing remains.  Nothing is read
-// from global memory twice.  The tile's meta words (slot eligibility) and
-// the purge bitmap (<= 512 B) sit in LDS as well: neighbouring lanes ask
-// for the same or the next row (broadcast or distinct banks), and the
-// bitmap test is one data-dependent ds_read_b32 for the few entries that
-// are not empty.
-constexpr int PURGE_THREADS = 256;
-constexpr int PURGE_ROWS = 256;        // rows per tile: one per thread
-constexpr int PURGE_VECS = 4;          // 16-byte loads in flight per thread
-constexpr int PURGE_MAX_BLOCKS = 2048; // 8 workgroups on each of 256 CUs
+// Row state: the row's meta word (slot eligibility) and a flag word to
+// which every lane reports what it did to an entry of the row (ROW_HIT:
+// cleared it; ROW_LIVE: it remains); thread r tombstones row r if it was
+// hit and nothing remains.  Neighbouring lanes ask for the same or the
+// next row: broadcast or distinct banks.  The purge bitmap (<= 512 B) sits
+// in LDS as well; the bitmap test is one data-dependent ds_read_b32 for
+// the few entries that are not empty.
 constexpr uint32_t ROW_HIT = 1u, ROW_LIVE = 2u;
 
 // One pod entry e read from *p, which lies in tile row `row`.
@@ -385,111 +504,61 @@ DEV void purge_entry(uint32_t e, uint32_t* p, int row,
   atomicOr(&s_flags[row], cleared ? ROW_HIT : ROW_LIVE);
 }
 
+struct PurgeSweep {
+  const Table& v;
+  const uint32_t* s_bits;
+  uint32_t n_bits;
+  int model_id;
+  uint32_t* s_meta;   // [SWEEP_ROWS]
+  uint32_t* s_flags;  // [SWEEP_ROWS]
+  uint32_t c[2] = {0, 0};  // entries cleared, keys tombstoned
+  DEV uint32_t row_load(uint64_t) const { return 0u; }
+  DEV void row_begin(int r, uint32_t m) {
+    s_meta[r] = m;
+    s_flags[r] = 0;
+  }
+  DEV void dword(uint32_t e, uint32_t row, uint32_t* p) {
+    purge_entry(e, p, (int)row, s_bits, n_bits, s_meta, model_id, s_flags,
+                c[0]);
+  }
+  DEV void vec(const uint32_t (&e)[4], const uint32_t (&r)[4], uint32_t vi,
+               uint32_t* tile_p) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dword(e[j], r[j], tile_p + vi * 4 + j);
+  }
+  DEV void row_end(int r, uint64_t row, uint32_t) {
+    if (s_flags[r] != ROW_HIT || (s_meta[r] & META_TOMB)) return;
+    const uint32_t old = atomicOr(&v.meta[row], META_TOMB);
+    c[1] += (old & META_TOMB) ? 0u : 1u;
+  }
+};
+
 // bits: the purge bitmap as n_bit_words 32-bit words (pod id pid is bit
 // pid % 32 of word pid / 32).  model_id -1: every model.  partials
-// [gridDim.x][2]: each workgroup's {entries cleared, keys tombstoned},
-// written once with plain stores - the op sums them after its one
-// readback, so no counter has to be zeroed before the launch.
-__global__ void __launch_bounds__(PURGE_THREADS) k_purge_pods(
+// [gridDim.x][2]: each workgroup's {entries cleared, keys tombstoned}.
+__global__ void __launch_bounds__(SWEEP_THREADS) k_purge_pods(
     Table v, const uint32_t* __restrict__ bits, int n_bit_words, int model_id,
     int64_t n_tiles, uint32_t* __restrict__ partials) {
   __shared__ uint32_t s_bits[128];
-  __shared__ uint32_t s_meta[PURGE_ROWS];
-  __shared__ uint32_t s_flags[PURGE_ROWS];
-  __shared__ uint32_t s_red[2 * (PURGE_THREADS / 64)];
-  const int tid = threadIdx.x;
-  const uint32_t P = (uint32_t)v.pods_per_key;
-  const uint64_t cap = v.cap_mask + 1;
-  const uint32_t n_bits = (uint32_t)n_bit_words * 32u;
-  if (tid < n_bit_words) s_bits[tid] = bits[tid];
-  uint32_t n_cleared = 0, n_tomb = 0;
-
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const uint64_t row0 = (uint64_t)tile * PURGE_ROWS;
-    const uint64_t rows_left = cap - row0;
-    const int rows = rows_left < PURGE_ROWS ? (int)rows_left : PURGE_ROWS;
-    const uint32_t n_dw = (uint32_t)rows * P;
-    const uint32_t n_vec = n_dw >> 2;
-    uint32_t* tile_p = v.pods + row0 * P;
-    const uint4* tile_v = reinterpret_cast<const uint4*>(tile_p);
-
-    // the meta load goes out first and is the only one waited for before
-    // the barrier; the first PURGE_VECS vector loads stay in flight
-    const uint32_t m_mine = tid < rows ? v.meta[row0 + tid] : 0u;
-    uint32_t base = 0;
-    do {
-      uint4 q[PURGE_VECS];
-#pragma unroll
-      for (int k = 0; k < PURGE_VECS; ++k) {
-        const uint32_t vi = base + k * PURGE_THREADS + tid;
-        q[k] = vi < n_vec ? tile_v[vi] : make_uint4(0, 0, 0, 0);
-      }
-      if (base == 0) {
-        s_meta[tid] = m_mine;
-        s_flags[tid] = 0;
-        __syncthreads();
-      }
-#pragma unroll
-      for (int k = 0; k < PURGE_VECS; ++k) {
-        const uint32_t vi = base + k * PURGE_THREADS + tid;
-        if ((q[k].x | q[k].y | q[k].z | q[k].w) == 0) continue;
-        const uint32_t i0 = vi * 4;
-        uint32_t row = i0 / P;
-        uint32_t col = i0 - row * P;
-        const uint32_t e[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          purge_entry(e[j], tile_p + i0 + j, (int)row, s_bits, n_bits, s_meta,
-                      model_id, s_flags, n_cleared);
-          if (++col == P) { col = 0; ++row; }
-        }
-      }
-      base += PURGE_THREADS * PURGE_VECS;
-    } while (base < n_vec);
-    // a tile whose dword count is no multiple of 4 (capacity 1 or 2 only)
-    if ((uint32_t)tid < (n_dw & 3u)) {
-      const uint32_t i = n_vec * 4 + tid;
-      purge_entry(tile_p[i], tile_p + i, (int)(i / P), s_bits, n_bits, s_meta,
-                  model_id, s_flags, n_cleared);
-    }
-    __syncthreads();
-    // thread r owns row r: it wrote the row's meta and flag words and is
-    // the one to rewrite them for the next tile, so no third barrier
-    if (tid < rows && s_flags[tid] == ROW_HIT && !(s_meta[tid] & META_TOMB)) {
-      const uint32_t old = atomicOr(&v.meta[row0 + tid], META_TOMB);
-      n_tomb += (old & META_TOMB) ? 0u : 1u;
-    }
-  }
-
-  // counters: wave, then workgroup, then one pair of stores
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_cleared += __shfl_down(n_cleared, off, 64);
-    n_tomb += __shfl_down(n_tomb, off, 64);
-  }
-  if ((tid & 63) == 0) {
-    s_red[2 * (tid >> 6)] = n_cleared;
-    s_red[2 * (tid >> 6) + 1] = n_tomb;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t c = 0, t = 0;
-    for (int w = 0; w < PURGE_THREADS / 64; ++w) {
-      c += s_red[2 * w];
-      t += s_red[2 * w + 1];
-    }
-    partials[2 * blockIdx.x] = c;
-    partials[2 * blockIdx.x + 1] = t;
-  }
+  __shared__ uint32_t s_meta[SWEEP_ROWS];
+  __shared__ uint32_t s_flags[SWEEP_ROWS];
+  // the walk's first barrier publishes the bitmap
+  if ((int)threadIdx.x < n_bit_words) s_bits[threadIdx.x] = bits[threadIdx.x];
+  PurgeSweep k{v, s_bits, (uint32_t)n_bit_words * 32u, model_id, s_meta,
+               s_flags};
+  sweep_table<false>(v, n_tiles, k);
+  wg_sum_store(k.c, partials + 2 * blockIdx.x);
 }
 
 // ---- remap pod ids -----------------------------------------------------
-// The purge's sweep with a code table in place of the bitmap: the same
-// tiles of PURGE_ROWS whole rows, the same 16-byte loads and per-row flag
-// words.  The table (remap_entry's codes, 2 B per id, only the n given)
-// is staged in LDS once per workgroup: 8 KB at n = 4096, 10 288 B static
-// LDS in all, and the translation is one data-dependent ds_read_u16 per
-// non-empty entry.  A moved entry reports ROW_LIVE, a dropped one ROW_HIT.
+// The purge with a code table in place of the bitmap, on a tile loop of
+// its own: on sweep_table the identity remap measured 1..5 % slower than
+// this loop under either load form (profiles/r11_table_sweeps.md), so the
+// kernel stays as it was, tails for capacity 1 and 2 included.  The table
+// (remap_entry's codes, 2 B per id, only the n given) is staged in LDS
+// once per workgroup: 8 KB at n = 4096, 10 288 B static LDS in all, and
+// the translation is one data-dependent ds_read_u16 per non-empty entry.
+// A moved entry reports ROW_LIVE, a dropped one ROW_HIT.
 //
 // The caller holds every other writer off (kvidx_ops.h), so entries and
 // meta are written with plain stores: a 16-byte vector in which a dword
@@ -511,19 +580,19 @@ DEV uint32_t remap_one(uint32_t e, int row, const uint16_t* s_codes,
 
 // remap: int32 [n], -1 = drop.  partials [gridDim.x][3]: each workgroup's
 // {entries moved, entries cleared, keys tombstoned}, as in k_purge_pods.
-__global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
+__global__ void __launch_bounds__(SWEEP_THREADS) k_remap_pods(
     Table v, const int32_t* __restrict__ remap, int n, int64_t n_tiles,
     uint32_t* __restrict__ partials) {
   __shared__ uint16_t s_codes[MAX_PODS];
-  __shared__ uint32_t s_meta[PURGE_ROWS];
-  __shared__ uint32_t s_flags[PURGE_ROWS];
-  __shared__ uint32_t s_red[3 * (PURGE_THREADS / 64)];
+  __shared__ uint32_t s_meta[SWEEP_ROWS];
+  __shared__ uint32_t s_flags[SWEEP_ROWS];
+  __shared__ uint32_t s_red[3 * (SWEEP_THREADS / 64)];
   const int tid = threadIdx.x;
   const uint32_t P = (uint32_t)v.pods_per_key;
   const uint64_t cap = v.cap_mask + 1;
   const uint32_t un = (uint32_t)n;
   // two codes per lane and store; the first tile's barrier publishes them
-  for (int i = 2 * tid; i < n; i += 2 * PURGE_THREADS) {
+  for (int i = 2 * tid; i < n; i += 2 * SWEEP_THREADS) {
     const uint32_t lo = (uint32_t)(remap[i] + 1);
     const uint32_t hi = i + 1 < n ? (uint32_t)(remap[i + 1] + 1) : 0u;
     reinterpret_cast<uint32_t*>(s_codes)[i >> 1] = lo | (hi << 16);
@@ -531,9 +600,9 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
   uint32_t n_moved = 0, n_cleared = 0, n_tomb = 0;
 
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const uint64_t row0 = (uint64_t)tile * PURGE_ROWS;
+    const uint64_t row0 = (uint64_t)tile * SWEEP_ROWS;
     const uint64_t rows_left = cap - row0;
-    const int rows = rows_left < PURGE_ROWS ? (int)rows_left : PURGE_ROWS;
+    const int rows = rows_left < SWEEP_ROWS ? (int)rows_left : SWEEP_ROWS;
     const uint32_t n_dw = (uint32_t)rows * P;
     const uint32_t n_vec = n_dw >> 2;
     uint32_t* tile_p = v.pods + row0 * P;
@@ -542,10 +611,10 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
     const uint32_t m_mine = tid < rows ? v.meta[row0 + tid] : 0u;
     uint32_t base = 0;
     do {
-      uint4 q[PURGE_VECS];
+      uint4 q[SWEEP_VECS];
 #pragma unroll
-      for (int k = 0; k < PURGE_VECS; ++k) {
-        const uint32_t vi = base + k * PURGE_THREADS + tid;
+      for (int k = 0; k < SWEEP_VECS; ++k) {
+        const uint32_t vi = base + k * SWEEP_THREADS + tid;
         q[k] = vi < n_vec ? tile_v[vi] : make_uint4(0, 0, 0, 0);
       }
       if (base == 0) {
@@ -554,8 +623,8 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
         __syncthreads();
       }
 #pragma unroll
-      for (int k = 0; k < PURGE_VECS; ++k) {
-        const uint32_t vi = base + k * PURGE_THREADS + tid;
+      for (int k = 0; k < SWEEP_VECS; ++k) {
+        const uint32_t vi = base + k * SWEEP_THREADS + tid;
         if ((q[k].x | q[k].y | q[k].z | q[k].w) == 0) continue;
         const uint32_t i0 = vi * 4;
         uint32_t row = i0 / P;
@@ -575,7 +644,7 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
         // vi < n_vec here: a vector past the tile was loaded as zeros
         if (changed) tile_v[vi] = make_uint4(e[0], e[1], e[2], e[3]);
       }
-      base += PURGE_THREADS * PURGE_VECS;
+      base += SWEEP_THREADS * SWEEP_VECS;
     } while (base < n_vec);
     // a tile whose dword count is no multiple of 4 (capacity 1 or 2 only)
     if ((uint32_t)tid < (n_dw & 3u)) {
@@ -609,15 +678,13 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
   __syncthreads();
   if (tid < 3) {
     uint32_t s = 0;
-    for (int w = 0; w < PURGE_THREADS / 64; ++w) s += s_red[3 * w + tid];
+    for (int w = 0; w < SWEEP_THREADS / 64; ++w) s += s_red[3 * w + tid];
     partials[3 * blockIdx.x + tid] = s;
   }
 }
 
 // ---- pod census --------------------------------------------------------
-// The third sweep of the family, and the read-only one: the purge's tiles
-// of PURGE_ROWS whole rows and its 16-byte loads, four in flight per lane,
-// but nothing goes back to the table.  What it keeps instead:
+// The read-only sweep: nothing goes back to the table.  What it keeps:
 //  - the pod x tier histogram, uint32 bins in dynamic LDS (num_pods *
 //    n_tiers words: 512 B for 64 pods x 2 tiers, 64 KB at MAX_PODS x
 //    MAX_TIERS), zeroed once per workgroup and carried across its
@@ -631,8 +698,8 @@ __global__ void __launch_bounds__(PURGE_THREADS) k_remap_pods(
 //    r], whose load went out with the meta load;
 //  - unknown-bin hits and the six scalar counters in registers.
 // Each workgroup leaves through plain stores into its row of partials
-// [gridDim.x][bins + 6]; k_census_reduce sums the rows.  No fill pass, no
-// global atomic, and no dword of the table is read twice.
+// [gridDim.x][bins + 6]; k_census_reduce sums the rows.  No fill pass and
+// no global atomic.
 constexpr uint32_t ROW_COUNT_SHIFT = 16;  // pods_per_key <= 4096: 13 bits
 constexpr uint32_t ROW_META_BITS = META_OCC | META_TOMB | META_MODEL_MASK;
 constexpr uint32_t ROW_COUNT_MASK = 0x3FFFu;
@@ -651,148 +718,69 @@ DEV void census_entry(uint32_t e, uint32_t rw, int model_id,
     atomicAdd(&s_hist[b], 1u);  // result unused: no return value asked for
 }
 
-// A table of fewer than 4 rows (capacity 1 or 2) can have fewer than 4
-// dwords, or a dword count that is no multiple of 4: one workgroup walks
-// it dword by dword.  Every larger table is whole vectors.
-DEV void census_tiny_table(const Table& v, int model_id, uint32_t num_pods,
-                           uint32_t n_tiers, uint32_t* s_hist, uint32_t* s_row,
-                           uint32_t& n_entries, uint32_t& n_unknown) {
-  const uint32_t P = (uint32_t)v.pods_per_key;
-  const uint32_t rows = (uint32_t)v.cap_mask + 1;
-  if (threadIdx.x < rows) s_row[threadIdx.x] = v.meta[threadIdx.x] & ROW_META_BITS;
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i < rows * P; i += PURGE_THREADS) {
-    const uint32_t e = v.pods[i];
-    census_entry(e, s_row[i / P], model_id, num_pods, n_tiers, s_hist,
-                 n_entries, n_unknown);
-    if (e != 0) atomicAdd(&s_row[i / P], 1u << ROW_COUNT_SHIFT);
+struct CensusSweep {
+  const Table& v;
+  int model_id;
+  uint32_t num_pods, n_tiers;
+  uint32_t* s_hist;  // [num_pods * n_tiers]
+  uint32_t* s_row;   // [SWEEP_ROWS]
+  // CensusSummary's order: live, tombstoned, full, entries, unknown, emap
+  uint32_t c[CENSUS_SUMMARY_LEN] = {0, 0, 0, 0, 0, 0};
+  DEV uint32_t row_load(uint64_t row) const { return v.e_meta[row]; }
+  DEV void row_begin(int r, uint32_t m) { s_row[r] = m & ROW_META_BITS; }
+  DEV void entry(uint32_t e, uint32_t rw) {
+    census_entry(e, rw, model_id, num_pods, n_tiers, s_hist, c[3], c[4]);
   }
-  __syncthreads();
-}
+  DEV void dword(uint32_t e, uint32_t row, uint32_t*) {
+    entry(e, s_row[row]);
+    if (e != 0) atomicAdd(&s_row[row], 1u << ROW_COUNT_SHIFT);
+  }
+  DEV void vec(const uint32_t (&e)[4], const uint32_t (&r)[4], uint32_t,
+               uint32_t*) {
+    uint32_t rw[4];  // the four row words in one round of LDS reads
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rw[j] = s_row[r[j]];
+    uint32_t run = 0;  // non-zero entries of the current row so far
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      entry(e[j], rw[j]);
+      run += e[j] != 0 ? 1u : 0u;
+      if (j == 3 || r[j + 1 < 4 ? j + 1 : 3] != r[j]) {
+        if (run) atomicAdd(&s_row[r[j]], run << ROW_COUNT_SHIFT);
+        run = 0;
+      }
+    }
+  }
+  // em: the engine-map word of the same slot
+  DEV void row_end(int r, uint64_t, uint32_t em) {
+    const uint32_t rw = s_row[r];
+    const CensusSlot s = census_slot(rw, model_id);
+    c[0] += s == CENSUS_LIVE;
+    c[1] += s == CENSUS_TOMB;
+    c[2] += s == CENSUS_LIVE &&
+            ((rw >> ROW_COUNT_SHIFT) & ROW_COUNT_MASK) ==
+                (uint32_t)v.pods_per_key;
+    c[5] += census_slot(em, model_id) == CENSUS_LIVE;
+  }
+};
 
-__global__ void __launch_bounds__(PURGE_THREADS) k_pod_census(
+__global__ void __launch_bounds__(SWEEP_THREADS) k_pod_census(
     Table v, int model_id, int num_pods, int n_tiers, int64_t n_tiles,
     uint32_t* __restrict__ partials) {
   extern __shared__ uint32_t s_hist[];  // [num_pods * n_tiers]
-  __shared__ uint32_t s_row[PURGE_ROWS];
-  __shared__ uint32_t s_red[CENSUS_SUMMARY_LEN * (PURGE_THREADS / 64)];
-  const int tid = threadIdx.x;
-  const uint32_t P = (uint32_t)v.pods_per_key;
-  const uint64_t cap = v.cap_mask + 1;
-  const uint32_t un_pods = (uint32_t)num_pods, un_tiers = (uint32_t)n_tiers;
-  const uint32_t bins = un_pods * un_tiers;
-  for (uint32_t i = tid; i < bins; i += PURGE_THREADS) s_hist[i] = 0;
-  // (the first tile's barrier publishes the zeros)
-  uint32_t n_live = 0, n_tomb = 0, n_full = 0, n_entries = 0, n_unknown = 0,
-           n_emap = 0;
-
-  // thread r owns row r: its word in s_row, and the engine-map word em
-  auto classify = [&](int rows, uint32_t em) {
-    if (tid >= rows) return;
-    const uint32_t rw = s_row[tid];
-    const CensusSlot c = census_slot(rw, model_id);
-    n_live += c == CENSUS_LIVE;
-    n_tomb += c == CENSUS_TOMB;
-    n_full += c == CENSUS_LIVE &&
-              ((rw >> ROW_COUNT_SHIFT) & ROW_COUNT_MASK) == P;
-    n_emap += census_slot(em, model_id) == CENSUS_LIVE;
-  };
-
-  if (cap < 4) {  // one tile, one workgroup (the op launches one)
-    if (blockIdx.x == 0) {
-      census_tiny_table(v, model_id, un_pods, un_tiers, s_hist, s_row,
-                        n_entries, n_unknown);
-      classify((int)cap, (uint64_t)tid < cap ? v.e_meta[tid] : 0u);
-    }
-    n_tiles = 0;
-  }
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    // capacity >= 4: a tile is 4..256 rows, a whole number of vectors
-    const uint64_t row0 = (uint64_t)tile * PURGE_ROWS;
-    const uint64_t rows_left = cap - row0;
-    const int rows = rows_left < PURGE_ROWS ? (int)rows_left : PURGE_ROWS;
-    const uint32_t n_vec = ((uint32_t)rows * P) >> 2;
-    const uint4* tile_v = reinterpret_cast<const uint4*>(v.pods + row0 * P);
-
-    // Every load is unconditional, at a clamped index, so that all of a
-    // round's loads go out back to back and each is waited for by its own
-    // count: meta first (the only one needed ahead of the barrier), e_meta
-    // right behind it (not looked at until the tile is done), then the
-    // vectors.  A lane past the end rereads the last row or vector, a
-    // line its neighbours fetch anyway, and drops it.
-    const uint64_t my_row = row0 + (uint32_t)(tid < rows ? tid : rows - 1);
-    const uint32_t m_mine = v.meta[my_row];
-    const uint32_t em_mine = v.e_meta[my_row];
-    uint32_t base = 0;
-    do {
-      uint4 q[PURGE_VECS];
-#pragma unroll
-      for (int k = 0; k < PURGE_VECS; ++k) {
-        const uint32_t vi = base + k * PURGE_THREADS + tid;
-        q[k] = tile_v[vi < n_vec ? vi : n_vec - 1];
-      }
-      if (base == 0) {
-        s_row[tid] = tid < rows ? (m_mine & ROW_META_BITS) : 0u;
-        __syncthreads();
-      }
-#pragma unroll
-      for (int k = 0; k < PURGE_VECS; ++k) {
-        const uint32_t vi = base + k * PURGE_THREADS + tid;
-        if (vi >= n_vec || (q[k].x | q[k].y | q[k].z | q[k].w) == 0) continue;
-        const uint32_t i0 = vi * 4;
-        const uint32_t e[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
-        // the tile row of each of the four dwords (all inside the tile),
-        // then the four row words in one round of LDS reads
-        uint32_t r[4];
-        r[0] = i0 / P;
-        uint32_t col = i0 - r[0] * P;
-#pragma unroll
-        for (int j = 1; j < 4; ++j) {
-          const bool wrap = ++col == P;
-          col = wrap ? 0u : col;
-          r[j] = r[j - 1] + (wrap ? 1u : 0u);
-        }
-        uint32_t rw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rw[j] = s_row[r[j]];
-        uint32_t run = 0;  // non-zero entries of the current row so far
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          census_entry(e[j], rw[j], model_id, un_pods, un_tiers, s_hist,
-                       n_entries, n_unknown);
-          run += e[j] != 0 ? 1u : 0u;
-          if (j == 3 || r[j + 1 < 4 ? j + 1 : 3] != r[j]) {
-            if (run) atomicAdd(&s_row[r[j]], run << ROW_COUNT_SHIFT);
-            run = 0;
-          }
-        }
-      }
-      base += PURGE_THREADS * PURGE_VECS;
-    } while (base < n_vec);
-    __syncthreads();
-    // thread r rewrites row r's word itself for the next tile, so no
-    // third barrier
-    classify(rows, em_mine);
-  }
-
-  // counters: wave, then workgroup; the barrier also closes the histogram
-  uint32_t c[CENSUS_SUMMARY_LEN] = {n_live,    n_tomb,    n_full,
-                                    n_entries, n_unknown, n_emap};
-#pragma unroll
-  for (int i = 0; i < CENSUS_SUMMARY_LEN; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c[i] += __shfl_down(c[i], off, 64);
-    if ((tid & 63) == 0) s_red[CENSUS_SUMMARY_LEN * (tid >> 6) + i] = c[i];
-  }
-  __syncthreads();
+  __shared__ uint32_t s_row[SWEEP_ROWS];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t bins = (uint32_t)num_pods * (uint32_t)n_tiers;
+  // (the walk's first barrier publishes the zeros)
+  for (uint32_t i = tid; i < bins; i += SWEEP_THREADS) s_hist[i] = 0;
+  CensusSweep k{v, model_id, (uint32_t)num_pods, (uint32_t)n_tiers, s_hist,
+                s_row};
+  sweep_table<true>(v, n_tiles, k);
+  // the barrier inside wg_sum_store also closes the histogram: no lane
+  // copies a bin out while another wave may still add to it
   uint32_t* mine = partials + (size_t)blockIdx.x * (bins + CENSUS_SUMMARY_LEN);
-  for (uint32_t i = tid; i < bins; i += PURGE_THREADS) mine[i] = s_hist[i];
-  if (tid < CENSUS_SUMMARY_LEN) {
-    uint32_t s = 0;
-    for (int w = 0; w < PURGE_THREADS / 64; ++w)
-      s += s_red[CENSUS_SUMMARY_LEN * w + tid];
-    mine[bins + tid] = s;
-  }
+  wg_sum_store(k.c, mine + bins);
+  for (uint32_t i = tid; i < bins; i += SWEEP_THREADS) mine[i] = s_hist[i];
 }
 
 // out[c] = sum over the n_rows workgroup rows of partials[r][c].  A thread
@@ -1546,6 +1534,44 @@ static const uint64_t* filter_ptr(const at::Tensor& filter_words) {
   return filter_words.numel() > 0 ? u64p(filter_words) : nullptr;
 }
 
+// What the three table sweeps launch with, after the checks they share:
+// min(tiles, SWEEP_MAX_BLOCKS, max_grid) workgroups, at least one, and an
+// unfilled int32 partials [grid, cols] for their counters.
+struct SweepLaunch {
+  int64_t n_tiles, grid;
+  at::Tensor partials;
+};
+static SweepLaunch plan_sweep(KVIDX_TABLE_PARAMS, const Table& v, int64_t cols,
+                              int64_t max_grid = SWEEP_MAX_BLOCKS) {
+  TORCH_CHECK(pods_per_key >= 1 && pods_per_key <= 4096,
+              "pods_per_key out of range");
+  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
+              "pods must hold capacity * pods_per_key entries");
+  TORCH_CHECK(meta.device() == keys.device() &&
+                  pods.device() == keys.device() &&
+                  e_meta.device() == keys.device(),
+              "table tensors must share one device");
+  // tiles are read as 16-byte vectors from the start of the array
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
+              "pods storage must be 16-byte aligned");
+  const int64_t n_tiles = (keys.numel() + SWEEP_ROWS - 1) / SWEEP_ROWS;
+  const int64_t grid = std::max<int64_t>(
+      1, std::min<int64_t>({n_tiles, (int64_t)SWEEP_MAX_BLOCKS, max_grid}));
+  return {n_tiles, grid,
+          at::empty({grid, cols}, keys.options().dtype(at::kInt))};
+}
+
+// The column sums of partials [grid, N], read back: the sweep's host wait.
+template <int N>
+static std::vector<int64_t> sum_partials(const at::Tensor& partials) {
+  auto host = partials.cpu();
+  const uint32_t* hp = u32p(host);
+  std::vector<int64_t> sums(N, 0);
+  for (int64_t b = 0; b < host.size(0); ++b)
+    for (int i = 0; i < N; ++i) sums[i] += hp[N * b + i];
+  return sums;
+}
+
 // The fused-score kernels hold a prompt's masks in LDS: up to 16 pod
 // words, 64 KB.  gpu_score_hashes and gpu_score_flat_tokens ask
 // fused_score_fits to choose their route; the launcher refuses what does
@@ -1743,29 +1769,12 @@ std::vector<int64_t> kvidx::gpu_purge_pods(KVIDX_TABLE_PARAMS,
   const int W = purge_words_checked(purge_words, model_id);
   TORCH_CHECK(purge_words.device() == keys.device(),
               "purge_words must live on the table's device");
-  TORCH_CHECK(pods_per_key >= 1 && pods_per_key <= 4096,
-              "pods_per_key out of range");
-  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
-              "pods must hold capacity * pods_per_key entries");
-  // tiles are read as 16-byte vectors from the start of the array
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
-              "pods storage must be 16-byte aligned");
-  const int64_t cap = keys.numel();
-  const int64_t n_tiles = (cap + PURGE_ROWS - 1) / PURGE_ROWS;
-  const int64_t grid = std::min<int64_t>(n_tiles, PURGE_MAX_BLOCKS);
-  auto partials = at::empty({grid, 2}, keys.options().dtype(at::kInt));
-  hipLaunchKernelGGL(k_purge_pods, dim3((unsigned)grid), dim3(PURGE_THREADS),
+  const SweepLaunch s = plan_sweep(KVIDX_TABLE_ARGS, v, 2);
+  hipLaunchKernelGGL(k_purge_pods, dim3((unsigned)s.grid), dim3(SWEEP_THREADS),
                      0, STREAM, v,
                      reinterpret_cast<const uint32_t*>(u64p(purge_words)),
-                     2 * W, (int)model_id, n_tiles, u32p(partials));
-  auto host = partials.cpu();  // waits for the sweep
-  const uint32_t* hp = u32p(host);
-  int64_t entries = 0, tombs = 0;
-  for (int64_t b = 0; b < grid; ++b) {
-    entries += hp[2 * b];
-    tombs += hp[2 * b + 1];
-  }
-  return {entries, tombs};
+                     2 * W, (int)model_id, s.n_tiles, u32p(s.partials));
+  return sum_partials<2>(s.partials);  // {entries cleared, keys tombstoned}
 }
 
 // The purge's launch shape; the map is validated on the host first (one
@@ -1776,27 +1785,11 @@ std::vector<int64_t> kvidx::gpu_remap_pods(KVIDX_TABLE_PARAMS,
   TORCH_CHECK(remap.device() == keys.device(),
               "remap must live on the table's device");
   const int n = remap_checked(remap);
-  TORCH_CHECK(pods_per_key >= 1 && pods_per_key <= 4096,
-              "pods_per_key out of range");
-  TORCH_CHECK(pods.numel() == keys.numel() * pods_per_key,
-              "pods must hold capacity * pods_per_key entries");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
-              "pods storage must be 16-byte aligned");
-  const int64_t cap = keys.numel();
-  const int64_t n_tiles = (cap + PURGE_ROWS - 1) / PURGE_ROWS;
-  const int64_t grid = std::min<int64_t>(n_tiles, PURGE_MAX_BLOCKS);
-  auto partials = at::empty({grid, 3}, keys.options().dtype(at::kInt));
-  hipLaunchKernelGGL(k_remap_pods, dim3((unsigned)grid), dim3(PURGE_THREADS),
-                     0, STREAM, v, i32p(remap), n, n_tiles, u32p(partials));
-  auto host = partials.cpu();  // waits for the sweep
-  const uint32_t* hp = u32p(host);
-  int64_t moved = 0, cleared = 0, tombs = 0;
-  for (int64_t b = 0; b < grid; ++b) {
-    moved += hp[3 * b];
-    cleared += hp[3 * b + 1];
-    tombs += hp[3 * b + 2];
-  }
-  return {moved, cleared, tombs};
+  const SweepLaunch s = plan_sweep(KVIDX_TABLE_ARGS, v, 3);
+  hipLaunchKernelGGL(k_remap_pods, dim3((unsigned)s.grid), dim3(SWEEP_THREADS),
+                     0, STREAM, v, i32p(remap), n, s.n_tiles,
+                     u32p(s.partials));
+  return sum_partials<3>(s.partials);  // {moved, cleared, keys tombstoned}
 }
 
 // The sweep, the reduce and one readback of bins + 6 int64 words, on the
@@ -1810,32 +1803,22 @@ std::vector<at::Tensor> kvidx::gpu_pod_census(KVIDX_TABLE_PARAMS,
   auto v = make_table_view(KVIDX_TABLE_ARGS, true);
   const int64_t bins =
       census_bins_checked(KVIDX_TABLE_ARGS, model_id, num_pods, n_tiers);
-  TORCH_CHECK(meta.device() == keys.device() &&
-                  pods.device() == keys.device() &&
-                  e_meta.device() == keys.device(),
-              "table tensors must share one device");
-  // tiles are read as 16-byte vectors from the start of the array
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.pods) % 16 == 0,
-              "pods storage must be 16-byte aligned");
-  const int64_t cap = keys.numel();
   const int64_t cols = bins + CENSUS_SUMMARY_LEN;
-  const int64_t n_tiles = (cap + PURGE_ROWS - 1) / PURGE_ROWS;
-  const int64_t grid = std::max<int64_t>(
-      1, std::min<int64_t>({n_tiles, (int64_t)PURGE_MAX_BLOCKS,
-                            CENSUS_PARTIAL_BYTES / (4 * cols)}));
+  const SweepLaunch s =
+      plan_sweep(KVIDX_TABLE_ARGS, v, cols, CENSUS_PARTIAL_BYTES / (4 * cols));
   // a workgroup's uint32 bins and counters cannot wrap
-  const int64_t tiles_per_wg = (n_tiles + grid - 1) / grid;
-  TORCH_CHECK(tiles_per_wg * PURGE_ROWS * pods_per_key < (1ll << 32),
+  const int64_t tiles_per_wg = (s.n_tiles + s.grid - 1) / s.grid;
+  TORCH_CHECK(tiles_per_wg * SWEEP_ROWS * pods_per_key < (1ll << 32),
               "table too large for 32-bit per-workgroup census counters");
-  auto partials = at::empty({grid, cols}, keys.options().dtype(at::kInt));
   auto sums = at::empty({cols}, keys.options().dtype(at::kLong));
-  hipLaunchKernelGGL(k_pod_census, dim3((unsigned)grid), dim3(PURGE_THREADS),
+  hipLaunchKernelGGL(k_pod_census, dim3((unsigned)s.grid), dim3(SWEEP_THREADS),
                      (size_t)bins * sizeof(uint32_t), STREAM, v, (int)model_id,
-                     (int)num_pods, (int)n_tiers, n_tiles, u32p(partials));
+                     (int)num_pods, (int)n_tiers, s.n_tiles,
+                     u32p(s.partials));
   hipLaunchKernelGGL(k_census_reduce,
                      dim3((unsigned)((cols + REDUCE_COLS - 1) / REDUCE_COLS)),
                      dim3(REDUCE_COLS * REDUCE_SLICES), 0, STREAM,
-                     u32p(partials), (int)grid, (int)cols,
+                     u32p(s.partials), (int)s.grid, (int)cols,
                      sums.data_ptr<int64_t>());
   auto err = hipGetLastError();
   TORCH_CHECK(err == hipSuccess, "pod census launch failed: ",

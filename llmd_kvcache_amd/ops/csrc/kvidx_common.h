@@ -582,6 +582,40 @@ KVIDX_HD int64_t probe_find(const uint64_t* __restrict__ keys,
   return -1;
 }
 
+// ---- table sweeps: tile geometry --------------------------------------
+// The purge, remap and census kernels read pods[C * P] as the flat array
+// it is, in tiles of SWEEP_ROWS whole rows taken as 16-byte vectors.  The
+// index arithmetic they trust is here, where a host program can walk it.
+static constexpr int SWEEP_THREADS = 256;
+static constexpr int SWEEP_ROWS = 256;        // rows per tile: one per thread
+static constexpr int SWEEP_VECS = 4;          // 16-byte loads in flight per thread
+static constexpr int SWEEP_MAX_BLOCKS = 2048; // 8 workgroups on each of 256 CUs
+
+struct SweepTile {
+  uint64_t row0;   // first table row
+  int rows;        // SWEEP_ROWS, or what is left
+  uint32_t n_vec;  // 16-byte vectors: rows * P / 4, whole from 4 rows on
+};
+KVIDX_HD SweepTile sweep_tile(uint64_t capacity, uint32_t P, int64_t tile) {
+  const uint64_t row0 = (uint64_t)tile * SWEEP_ROWS;
+  const uint64_t left = capacity - row0;
+  const int rows = left < SWEEP_ROWS ? (int)left : SWEEP_ROWS;
+  return {row0, rows, ((uint32_t)rows * P) >> 2};
+}
+
+// r[j]: the tile row of dword j of the tile's vector vi.  One division by
+// the runtime P per vector; the wraps are selects, not branches.
+KVIDX_HD void sweep_vec_rows(uint32_t vi, uint32_t P, uint32_t (&r)[4]) {
+  const uint32_t i0 = vi * 4;
+  r[0] = i0 / P;
+  uint32_t col = i0 - r[0] * P;
+  for (int j = 1; j < 4; ++j) {
+    const bool wrap = ++col == P;
+    col = wrap ? 0u : col;
+    r[j] = r[j - 1] + (wrap ? 1u : 0u);
+  }
+}
+
 // ---- purge by pod -----------------------------------------------------
 // A purge bitmap is W 64-bit words; bit pid % 64 of word pid / 64 selects
 // pod id pid.  Tier bits of an entry never take part.

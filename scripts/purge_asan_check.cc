@@ -9,7 +9,8 @@
 // element past any of them is a sanitizer report.  Every pods_per_key
 // from 1 to 17 runs with bitmaps of 1, 2 and 64 words, entries whose ids
 // lie past the bitmap's end, and ids at every word edge; the counts are
-// held against a direct recount.
+// held against a direct recount.  Ahead of that, the tile geometry of the
+// device sweeps is walked on the host (check_sweep_geometry).
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -24,7 +25,56 @@ static int fail(const char* what, int P, int W) {
   return 1;
 }
 
+// The tile geometry that k_purge_pods, k_remap_pods and k_pod_census trust
+// (sweep_tile, sweep_vec_rows), walked as the device walker walks it:
+// tiles by grid stride, rounds of SWEEP_VECS vectors per thread, a vector
+// past the tile dropped.  Every dword of pods[C * P] must be visited
+// exactly once, with tile row i / P - row0, inside its tile.  `seen` is
+// exactly C * P bytes, so an index past the array is a sanitizer report.
+// (A failure prints the capacity where the purge check prints W.)
+static int check_sweep_geometry() {
+  for (int P = 1; P <= 17; ++P) {
+    for (uint64_t cap : {4, 64, 256, 1024}) {
+      std::vector<uint8_t> seen(cap * P, 0);
+      const int64_t n_tiles = (int64_t)((cap + SWEEP_ROWS - 1) / SWEEP_ROWS);
+      const int64_t grid = n_tiles < 3 ? n_tiles : 3;  // a stride to take
+      for (int64_t block = 0; block < grid; ++block) {
+        for (int64_t tile = block; tile < n_tiles; tile += grid) {
+          const SweepTile t = sweep_tile(cap, (uint32_t)P, tile);
+          if (t.rows < 4 || t.rows > SWEEP_ROWS || t.row0 + t.rows > cap ||
+              (uint64_t)t.n_vec * 4 != (uint64_t)t.rows * P)
+            return fail("tile shape", P, (int)cap);
+          uint32_t base = 0;
+          do {
+            for (int tid = 0; tid < SWEEP_THREADS; ++tid) {
+              for (int k = 0; k < SWEEP_VECS; ++k) {
+                const uint32_t vi = base + k * SWEEP_THREADS + tid;
+                if (vi >= t.n_vec) continue;
+                uint32_t r[4];
+                sweep_vec_rows(vi, (uint32_t)P, r);
+                for (int j = 0; j < 4; ++j) {
+                  const uint64_t i = t.row0 * P + (uint64_t)vi * 4 + j;
+                  if (r[j] >= (uint32_t)t.rows)
+                    return fail("row outside its tile", P, (int)cap);
+                  if (r[j] != i / P - t.row0)
+                    return fail("row of a dword", P, (int)cap);
+                  ++seen[i];
+                }
+              }
+            }
+            base += SWEEP_THREADS * SWEEP_VECS;
+          } while (base < t.n_vec);
+        }
+      }
+      for (uint8_t n : seen)
+        if (n != 1) return fail("dword not visited exactly once", P, (int)cap);
+    }
+  }
+  return 0;
+}
+
 int main() {
+  if (check_sweep_geometry()) return 1;
   std::mt19937_64 rng(4242);
   const uint64_t cap = 64;
   const uint32_t edge_ids[] = {0, 1, 62, 63, 64, 65, 126, 127, 128,

@@ -30,6 +30,9 @@ OCC, TOMB = 0x80000000, 0x40000000
 # model filter and content of the issue's lists at least once.  2^20 rows
 # is where a workgroup takes a second tile; 4096 x 4 is the 64 KB histogram.
 CASES = [
+    (1, 1, 1, 1, -1, "same"),     # under 4 rows: the dword-by-dword path
+    (2, 3, 1, 1, -1, "same"),
+    (4, 3, 64, 2, -1, "full"),    # the smallest table read as vectors
     (64, 1, 1, 1, -1, "same"),
     (64, 10, 64, 2, 1, "unknown"),
     (1024, 3, 130, 4, -1, "dead"),

@@ -45,9 +45,11 @@ N_PODS = 130
 
 # A workgroup takes tiles of 256 rows and the grid is capped at 2048
 # workgroups, so the grid-stride loop turns only from 2^19 rows on: the
-# last shape is there for it (two tiles per workgroup).
-SHAPES = [(64, 1), (64, 10), (1024, 3), (1024, 10), (65536, 10),
-          (65536, 16), (1 << 20, 10)]
+# last shape is there for it (two tiles per workgroup).  Capacities 1 and 2
+# take the dword-by-dword path; (4, 3) is the smallest table on the vector
+# path: 3 vectors, the last all zero, every lane but three past the end.
+SHAPES = [(1, 1), (2, 3), (4, 3), (64, 1), (64, 10), (1024, 3), (1024, 10),
+          (65536, 10), (65536, 16), (1 << 20, 10)]
 BITMAPS = {
     "empty": [],
     "one": [63],
@@ -60,6 +62,24 @@ BITMAPS = {
 def _reference_state(capacity, P):
     """The CPU-built table of one shape, as a state dict; built once and
     only ever copied from."""
+    if capacity <= 4:
+        # random_table needs room; by hand: a row that pod 63 alone empties
+        # (model 1), a row that loses 64 and keeps the rest unless all go
+        # (model 0), a tombstone with a stale entry, an unoccupied row
+        rows = [
+            (cases.OCC | 1, [cases.entry(63, k % 4) for k in range(P)]),
+            (cases.OCC, [cases.entry((64, 5, 129)[k % 3], k % 4)
+                         for k in range(P)]),
+            (cases.OCC | cases.TOMB | 1, [cases.entry(63, 3)] + [0] * (P - 1)),
+            (0, [0] * P),
+        ][:capacity]
+        t = KvTable(TableIndexConfig(capacity=capacity, pods_per_key=P))
+        t.keys.copy_(torch.arange(1, capacity + 1))
+        t.meta.copy_(torch.tensor([cases.i32(m) for m, _ in rows],
+                                  dtype=torch.int32))
+        t.pods.copy_(torch.tensor([cases.i32(e) for _, es in rows for e in es],
+                                  dtype=torch.int32))
+        return t.state_dict()
     return cases.random_table(capacity, P, n_pods=N_PODS,
                               seed=capacity + P).state_dict()
 

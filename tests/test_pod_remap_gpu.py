@@ -39,8 +39,10 @@ N_PODS = 130
 
 # Tiles of 256 rows under a 2048-workgroup cap (the purge's launch shape):
 # 2^20 rows is the smallest capacity at which a workgroup takes a second
-# tile.  Capacities 1 and 2 are the only ones with a dword tail.
-SHAPES = [(1, 1), (2, 3), (64, 10), (512, 3), (1024, 10), (1024, 16),
+# tile.  Capacities 1 and 2 are no whole vectors and go dword by dword;
+# (4, 3) is the smallest table on the vector path: 3 vectors, every lane
+# but three past the end.
+SHAPES = [(1, 1), (2, 3), (4, 3), (64, 10), (512, 3), (1024, 10), (1024, 16),
           (1 << 20, 10)]
 
 
@@ -76,9 +78,10 @@ def _reference_state(capacity, P):
     only ever copied from.  Pod 4095 is planted so the last id has
     entries to move."""
     if capacity <= 2:
-        # every dword of the tail in use: one live row per slot
+        # every dword in use: one live row per slot, the first of them all
+        # ids that the drop-only test purges
         t = KvTable(TableIndexConfig(capacity=capacity, pods_per_key=P))
-        ids = (63, 5, 4095, 64, 129, 0)
+        ids = (63, 0, 4095, 64, 129, 5)
         t.meta.fill_(pc.i32(pc.OCC))
         t.keys.copy_(torch.arange(1, capacity + 1))
         t.pods.copy_(torch.tensor(
@@ -174,7 +177,8 @@ def test_two_dropping_lanes_tombstone_the_row_once(P, slots):
     assert int((rows != 0).sum()) == mixed.numel()
 
 
-@pytest.mark.parametrize("capacity,P", [(64, 10), (1024, 3), (1024, 16)])
+@pytest.mark.parametrize("capacity,P",
+                         [(2, 3), (64, 10), (1024, 3), (1024, 16)])
 def test_drop_only_remap_is_the_gpu_purge(capacity, P):
     _, a = _pair(capacity, P)
     _, b = _pair(capacity, P)
