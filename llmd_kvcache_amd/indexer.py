@@ -325,6 +325,35 @@ class Indexer:
         Returns the [B, num_pods] float32 score tensor (CPU or device),
         columns in pod-id order: hold the registry's ids_shared() around
         this call and scores_to_map, or check registry.pod_generation."""
+        return self._read_flat_tokens(tokens_flat, offsets, model_name,
+                                      pod_identifiers, None)
+
+    def top_pods_flat_tokens(
+        self,
+        tokens_flat,
+        offsets,
+        model_name: str,
+        pod_identifiers: Sequence[str],
+        top_n: int,
+    ):
+        """score_flat_tokens with each prompt's best top_n pods
+        (1..MAX_TOPK) picked where the scores are computed, by the same
+        plan_read_route decision.  Returns (ids int32 [B, top_n], scores
+        float32 [B, top_n]) tensors (CPU or device): pods that score > 0,
+        highest score first, equal scores by ascending pod id, (-1, 0.0)
+        in unused slots.  The ids are registry pod ids: hold the
+        registry's ids_shared() around this call and top_to_lists."""
+        from .kvblock.gpu_index import check_top_n, check_topk_weights
+
+        check_top_n(top_n)
+        check_topk_weights(b.weight for b in self.config.backend_configs)
+        return self._read_flat_tokens(tokens_flat, offsets, model_name,
+                                      pod_identifiers, top_n)
+
+    def _read_flat_tokens(self, tokens_flat, offsets, model_name,
+                          pod_identifiers, top_n):
+        """The routes of score_flat_tokens; top_n None ends them in the
+        score matrix, a number in the top-n pair."""
         import torch
 
         from .kvblock.gpu_index import _to_i64
@@ -341,11 +370,13 @@ class Indexer:
             # chain function, same walk, the same scores bit for bit
             a = idx.score_args(model_name, pod_identifiers,
                                self.config.backend_configs)
-            return idx.table.ops.gpu_score_flat_tokens(
-                *idx.table._t(), tokens_flat, offsets, a.model_id,
-                a.filter_words, a.weights, a.num_pods,
-                idx.table.next_epoch(), init, bs, a.n_tiers,
-                hashing.NATIVE_ALGO_IDS[tp.config.hash_algo])
+            args = (*idx.table._t(), tokens_flat, offsets, a.model_id,
+                    a.filter_words, a.weights, a.num_pods,
+                    idx.table.next_epoch(), init, bs, a.n_tiers,
+                    hashing.NATIVE_ALGO_IDS[tp.config.hash_algo])
+            if top_n is None:
+                return idx.table.ops.gpu_score_flat_tokens(*args)
+            return tuple(idx.table.ops.gpu_topk_flat_tokens(*args, top_n))
         parents = torch.full((B,), init, dtype=torch.int64)
         hashes, chunk_off = idx.table.ops.hash_chain_batch(
             tokens_flat, offsets, parents, bs,
@@ -354,19 +385,61 @@ class Indexer:
         max_k = int(counts.max()) if B else 0
         num_pods = idx._num_pods_padded()
         if max_k == 0:
-            return torch.zeros((B, num_pods), dtype=torch.float32)
+            if top_n is None:
+                return torch.zeros((B, num_pods), dtype=torch.float32)
+            return (torch.full((B, top_n), -1, dtype=torch.int32),
+                    torch.zeros((B, top_n), dtype=torch.float32))
         weights = idx.tier_weights(
             {b.name: b.weight for b in self.config.backend_configs}
         )
-        fused = idx.fused_scores
+        if top_n is None:
+            fused, kw = idx.fused_scores, {}
+        else:
+            fused, kw = idx.fused_top_pods, {"top_n": top_n}
         if idx.table.is_cuda:
             device = idx.device
             return fused(hashes.to(device),
                          chunk_off.to(torch.int32).to(device),
                          model_name, set(pod_identifiers), weights,
-                         max_k=max_k)
+                         max_k=max_k, **kw)
         return fused(hashes, counts, model_name,
-                     set(pod_identifiers), weights, max_k=max_k)
+                     set(pod_identifiers), weights, max_k=max_k, **kw)
+
+    def top_pods_tokens_batch(
+        self,
+        token_lists: Sequence[Sequence[int]],
+        model_name: str,
+        pod_identifiers: Sequence[str],
+        top_n: int,
+    ) -> List[List[tuple]]:
+        """Each prompt's best top_n pods (1..MAX_TOPK, else ValueError) as
+        [(pod, score), ...], highest score first, pods that score 0 left
+        out; works on every backend.
+
+        Table backends (fused_top_pods) pick on the table's device and
+        order equal scores by LOWEST POD ID.  Every other backend, and a
+        table backend under a hash algorithm without a native chain, sorts
+        the score_tokens_batch maps by (-score, pod name): equal scores
+        are then in name order, which is id order only where the names
+        were interned in that order."""
+        from .kvblock.gpu_index import check_top_n
+
+        check_top_n(top_n)
+        idx = self._kv_block_index
+        tp = self.tokens_processor
+        if (getattr(idx, "fused_top_pods", None) is not None
+                and tp._native is not None
+                and tp.config.hash_algo in hashing.NATIVE_ALGO_IDS):
+            flat, off = pack_token_lists(token_lists)
+            with self._ids_shared():
+                ids, scores = self.top_pods_flat_tokens(
+                    flat, off, model_name, pod_identifiers, top_n)
+                return idx.top_to_lists(ids, scores)
+        maps = self.score_tokens_batch(token_lists, model_name,
+                                       pod_identifiers)
+        return [sorted(((p, s) for p, s in m.items() if s > 0),
+                       key=lambda ps: (-ps[1], ps[0]))[:top_n]
+                for m in maps]
 
     def _score_keys_batch(
         self, keys_per_prompt, model_name: str,

@@ -42,6 +42,25 @@ MAX_TIERS = 4
 DEFAULT_CAPACITY = 1 << 21  # 2M slots; ~1M keys at 0.5 load factor
 DEFAULT_PODS_PER_KEY = 10  # in_memory.go:34
 MAX_PODS = 4096
+MAX_TOPK = 16  # kvidx_common.h
+
+
+def check_top_n(top_n) -> int:
+    """top_n of the top-n entry points: an integer in 1..MAX_TOPK."""
+    if (isinstance(top_n, bool) or not isinstance(top_n, int)
+            or not 1 <= top_n <= MAX_TOPK):
+        raise ValueError(f"top_n must be an integer in 1..{MAX_TOPK}, "
+                         f"got {top_n!r}")
+    return top_n
+
+
+def check_topk_weights(weights) -> None:
+    """Tier weights of the top-n entry points (floats, or a tensor: read
+    on the host): the rank key orders a score by its bit pattern, which
+    holds for sums of weights that are >= 0 and not NaN."""
+    vals = weights.tolist() if hasattr(weights, "tolist") else list(weights)
+    if any(not w >= 0 for w in vals):
+        raise ValueError(f"top-n needs tier weights >= 0, got {vals}")
 
 
 def _to_i64(h: int) -> int:
@@ -363,6 +382,25 @@ class KvTable:
         return self.ops.cpu_fused_score(
             *self._t(), hashes, counts_or_offsets, model_id, filter_words,
             weights, num_pods, self.next_epoch())
+
+    def top_hashes(self, hashes, counts_or_offsets, model_id, filter_words,
+                   weights, num_pods, top_n, max_k=None, n_tiers=MAX_TIERS):
+        """score_hashes with each prompt's best top_n pods picked where
+        the scores are: (ids int32, scores float32), both [B, top_n], in
+        the rank_key order of kvidx_common.h ((-1, 0.0) where fewer pods
+        score).  On a GPU table inside the fused kernel, or by
+        k_topk_rows behind the split route; on a CPU table by
+        cpu_score_topk over the matrix."""
+        if self.is_cuda:
+            ids, top = self.ops.gpu_topk_hashes(
+                *self._t(), hashes, counts_or_offsets, model_id, filter_words,
+                weights, num_pods, self.next_epoch(),
+                max_k if max_k is not None else 512, n_tiers, top_n)
+        else:
+            ids, top = self.ops.cpu_score_topk(
+                self.score_hashes(hashes, counts_or_offsets, model_id,
+                                  filter_words, weights, num_pods), top_n)
+        return ids, top
 
     def compact(self, new_capacity: Optional[int] = None) -> None:
         """Rehash every live entry into a fresh tensor bundle, dropping
@@ -736,6 +774,39 @@ class TableIndex(Index):
             return self.table.score_hashes(
                 hashes, counts_or_offsets, a.model_id, a.filter_words,
                 a.weights, a.num_pods, max_k, a.n_tiers)
+
+    def fused_top_pods(self, hashes: torch.Tensor,
+                       counts_or_offsets: torch.Tensor, model_name: str,
+                       pod_identifier_set: Set[str],
+                       weights: Optional[torch.Tensor] = None,
+                       max_k: Optional[int] = None, top_n: int = 1
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """fused_scores with the pick made where the scores are: each
+        prompt's best top_n pods (1..MAX_TOPK) as (ids int32 [B, top_n],
+        scores float32 [B, top_n]) on the table's device.  Only pods that
+        score > 0 appear, highest score first, equal scores by ascending
+        pod id; unused slots hold (-1, 0.0).  Negative or NaN weights are
+        a ValueError.  The ids are registry pod ids: the id-gate rule of
+        fused_scores holds until top_to_lists has made names of them."""
+        check_top_n(top_n)
+        a = self.score_args(model_name, pod_identifier_set, weights=weights)
+        check_topk_weights(a.weights)
+        with nullcontext() if self.table.is_cuda else self._write_lock:
+            return self.table.top_hashes(
+                hashes, counts_or_offsets, a.model_id, a.filter_words,
+                a.weights, a.num_pods, top_n, max_k, a.n_tiers)
+
+    def top_to_lists(self, ids: torch.Tensor, scores: torch.Tensor
+                     ) -> List[List[Tuple[str, float]]]:
+        """(ids, scores) [B, top_n] -> per prompt [(pod, score), ...] in
+        the order given.  One host copy of each of the two small tensors;
+        -1 (no candidate) and released ids are skipped."""
+        names = list(self.registry.id_to_pod)  # "" = released id
+        n_names = len(names)
+        return [[(names[i], s) for i, s in zip(row_i, row_s)
+                 if 0 <= i < n_names and names[i]]
+                for row_i, row_s in zip(ids.cpu().tolist(),
+                                        scores.cpu().tolist())]
 
     def tier_weights(self, weight_map: Optional[Dict[str, float]] = None
                      ) -> torch.Tensor:

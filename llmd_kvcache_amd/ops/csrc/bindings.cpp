@@ -31,6 +31,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cpu_fused_score", &kvidx::cpu_fused_score);
   m.def("cpu_score_from_masks", &kvidx::cpu_score_from_masks);
   m.def("cpu_get_request_keys", &kvidx::cpu_get_request_keys);
+  m.def("cpu_score_topk", &kvidx::cpu_score_topk, py::arg("scores"),
+        py::arg("top_n"));
+  m.attr("MAX_TOPK") = kvidx::MAX_TOPK;
 #ifdef KVIDX_WITH_HIP
   m.attr("HAS_HIP") = true;
   m.def("gpu_insert", &kvidx::gpu_insert);
@@ -67,6 +70,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
         py::arg("block_size"), py::arg("n_tiers"), py::arg("algo") = 0,
         py::call_guard<py::gil_scoped_release>());
+  // score top-n: {ids, scores} [B, top_n] in the rank_key order
+  m.def("gpu_fused_topk", &kvidx::gpu_fused_topk);
+  m.def("gpu_fused_topk_rows", &kvidx::gpu_fused_topk_rows);
+  m.def("gpu_topk_rows", &kvidx::gpu_topk_rows, py::arg("scores"),
+        py::arg("top_n"));
+  m.def("gpu_topk_hashes", &kvidx::gpu_topk_hashes);
+  // stage + chain + top-n in one call; the GIL is released for all of it
+  m.def("gpu_topk_flat_tokens", &kvidx::gpu_topk_flat_tokens,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("offsets"),
+        py::arg("model_id"), py::arg("filter_words"), py::arg("weights"),
+        py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("n_tiers"), py::arg("algo"),
+        py::arg("top_n"), py::call_guard<py::gil_scoped_release>());
   m.def("gpu_apply_events", &kvidx::gpu_apply_events,
         py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
         py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),

@@ -7,7 +7,9 @@
 // Thread-safety is provided by the Python-side caller (one writer at a
 // time); the GPU path uses atomics instead (hip_ops.hip).
 
+#include <algorithm>
 #include <cstring>
+#include <functional>
 
 #include "kvidx_ops.h"
 
@@ -334,6 +336,38 @@ at::Tensor kvidx::cpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
     }
   });
   return scores;
+}
+
+// Score top-n over a host matrix: each row's rank keys, the top_n largest
+// in front, cut at the first non-candidate.  Keys of a row are pairwise
+// distinct, so the order is total and the result unique.
+std::vector<at::Tensor> kvidx::cpu_score_topk(at::Tensor scores,
+                                              int64_t top_n) {
+  TORCH_CHECK(!scores.is_cuda(), "scores must live on the host");
+  const int64_t P = topk_rows_checked(scores, top_n);
+  const int64_t B = scores.size(0);
+  auto ids = at::empty({B, top_n}, at::kInt);
+  auto out = at::empty({B, top_n}, at::kFloat);
+  const float* sp = scores.data_ptr<float>();
+  int32_t* ip = ids.data_ptr<int32_t>();
+  float* op = out.data_ptr<float>();
+  const int64_t n = std::min(top_n, P);
+  at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
+    std::vector<uint64_t> key(P);
+    for (int64_t b = begin; b < end; ++b) {
+      for (int64_t c = 0; c < P; ++c)
+        key[c] = rank_key(sp[b * P + c], (uint32_t)c);
+      std::partial_sort(key.begin(), key.begin() + n, key.end(),
+                        std::greater<uint64_t>());
+      for (int64_t r = 0; r < top_n; ++r) {
+        // a non-candidate unpacks to (-1, 0.0f), and so does a slot past P
+        const uint64_t k = r < n ? key[r] : 0;
+        ip[b * top_n + r] = rank_key_id(k);
+        op[b * top_n + r] = rank_key_score(k);
+      }
+    }
+  });
+  return {ids, out};
 }
 
 void kvidx::cpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,

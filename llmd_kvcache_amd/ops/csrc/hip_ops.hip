@@ -863,19 +863,133 @@ DEV int score_walk_step(const unsigned long long* mk, int W, int n_tiers,
   return act;
 }
 
+// ---- score top-n: selection (the contract: kvidx_common.h rank_key) -----
+// Two device functions under k_fused_topk[_rows] and k_topk_rows.
+
+// Wave-wide unsigned 64-bit maximum, returned in scalar registers: every
+// lane ends the butterfly with the same value, and saying so lets the
+// rounds below compare against it and branch on it as scalars.
+DEV uint64_t wave_max_u64(uint64_t x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint64_t y = __shfl_xor(x, off, 64);
+    x = y > x ? y : x;
+  }
+  // the builtin returns int: without the casts the low word sign-extends
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32));
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// Selection inside a wave, no removal.  A lane holds N rank keys in
+// registers; round r takes the wave maximum over the keys strictly below
+// round r - 1's winner.  Keys of different pods are never equal, so the
+// bound stands in for removing the winner: key[] is only ever indexed by
+// the unrolled i (a runtime index would put it behind gpr_idx moves or in
+// scratch), and no lane diverges.  Returns round `lane`'s winner in lanes
+// 0..top_n-1 and 0 (no candidate) everywhere else; the rounds stop at the
+// first wave maximum that is no candidate.
+template <int N>
+DEV uint64_t wave_topk(const uint64_t (&key)[N], int top_n, int lane) {
+  uint64_t bound = ~0ull;  // above every key: a finite score's bits
+  uint64_t mine = 0;
+  for (int r = 0; r < top_n; ++r) {
+    uint64_t m = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      m = (key[i] < bound && key[i] > m) ? key[i] : m;
+    bound = wave_max_u64(m);
+    if (bound < RANK_KEY_MIN) break;
+    mine = lane == r ? bound : mine;
+  }
+  return mine;
+}
+
+// Merge across the workgroup's four waves and store one prompt's result
+// rows.  mine: wave_topk's return.  xch: uint64 [4][MAX_TOPK] in LDS that
+// nobody reads any more.  Each wave parks its MAX_TOPK slots (zeros past
+// its winners, so nothing stale is ever read); after one barrier wave 0
+// takes one parked key per lane, 4 x 16 = 64 exactly, runs the same rounds
+// and lanes 0..top_n-1 store: ids and scores are one contiguous store of
+// at most 64 B each, and every slot is written ((-1, 0.0f) where the
+// candidates ran out).
+DEV void wg_topk_store(uint64_t mine, uint64_t* xch, int top_n,
+                       int32_t* __restrict__ ids_row,
+                       float* __restrict__ scores_row) {
+  static_assert(4 * MAX_TOPK == 64, "one parked key per lane of wave 0");
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (lane < MAX_TOPK) xch[wave * MAX_TOPK + lane] = mine;
+  __syncthreads();
+  if (wave != 0) return;
+  const uint64_t parked[1] = {xch[lane]};
+  const uint64_t win = wave_topk(parked, top_n, lane);
+  if (lane < top_n) {
+    ids_row[lane] = rank_key_id(win);
+    scores_row[lane] = rank_key_score(win);
+  }
+}
+
+// What a top-n kernel writes: ids int32 [B, top_n], scores float32
+// [B, top_n].
+struct TopkOut {
+  int32_t* __restrict__ ids;
+  float* __restrict__ scores;
+  int top_n;
+};
+
+// Epilogue policies of fused_score_body.  word() is called by every lane
+// once per 64-pod word its wave walked, with the pod's final score;
+// finish() once by every thread after the walk, with the dynamic LDS.
+//
+// ScoreStore: the [B, num_pods] matrix (k_fused_score[_rows]).
+struct ScoreStore {
+  float* __restrict__ scores;
+  DEV void word(int b, int pid, int num_pods, float score) {
+    if (pid < num_pods) scores[(size_t)b * num_pods + pid] = score;
+  }
+  DEV void finish(int, unsigned long long*) {}
+};
+
+// ScoreTopk: nothing per pod leaves the registers.  A wave walks words
+// wave, wave + 4, ...: at most four because W <= 16, so a lane ends with
+// at most four keys.  They sit in a four-deep shift register, which takes
+// the walk's runtime word loop without a runtime-indexed array; unused
+// places stay 0.  The exchange area overlays the front of the mask area:
+// the first barrier is the last wave's walk, after it nobody reads masks.
+struct ScoreTopk {
+  TopkOut out;
+  uint64_t key[4] = {0, 0, 0, 0};
+  DEV void word(int, int pid, int num_pods, float score) {
+    key[3] = key[2];
+    key[2] = key[1];
+    key[1] = key[0];
+    key[0] = pid < num_pods ? rank_key(score, (uint32_t)pid) : 0ull;
+  }
+  DEV void finish(int b, unsigned long long* lds) {
+    const uint64_t mine = wave_topk(key, out.top_n, threadIdx.x & 63);
+    __syncthreads();
+    wg_topk_store(mine, reinterpret_cast<uint64_t*>(lds), out.top_n,
+                  out.ids + (size_t)b * out.top_n,
+                  out.scores + (size_t)b * out.top_n);
+  }
+};
+
 // Fused probe + longest-prefix score. One workgroup per prompt; dynamic
 // LDS holds the per-key per-tier masks; the four waves then walk keys in
 // order, a 64-pod word each, with the active pod set in registers.
 //
-// The body is shared by two entries that differ only in where prompt b's
-// keys lie: k_fused_score takes flat hashes with offsets [B+1],
-// k_fused_score_rows takes padded rows (h = hashes + b * stride, K =
-// n_keys[b]) as the row-major chain kernel leaves them.
+// The body is shared by four entries.  They differ in where prompt b's
+// keys lie: k_fused_score and k_fused_topk take flat hashes with offsets
+// [B+1], k_fused_score_rows and k_fused_topk_rows take padded rows (h =
+// hashes + b * stride, K = n_keys[b]) as the row-major chain kernel
+// leaves them; and in the epilogue policy, the score matrix or top-n.
+template <typename Epilogue>
 DEV void fused_score_body(
     Table v, const uint64_t* __restrict__ h, const int K,
     uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
     const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
-    int n_tiers, float* __restrict__ scores) {
+    int n_tiers, Epilogue epi) {
   // n_tiers = tiers actually registered (usually 1-2, <= MAX_TIERS):
   // sizing LDS by it instead of MAX_TIERS keeps 256-pod fleets (W=4)
   // at 16-32 KB/WG instead of 64 KB, preserving occupancy.
@@ -909,9 +1023,9 @@ DEV void fused_score_body(
                           weights, lane, k == 0, active, score);
       if (!__any(act)) break;  // this word's active set is empty
     }
-    int pid = w * 64 + lane;
-    if (pid < num_pods) scores[(size_t)b * num_pods + pid] = score;
+    epi.word(b, w * 64 + lane, num_pods, score);
   }
+  epi.finish(b, lds_masks);
 }
 
 __global__ void __launch_bounds__(256) k_fused_score(
@@ -923,7 +1037,21 @@ __global__ void __launch_bounds__(256) k_fused_score(
   const int b = blockIdx.x;
   fused_score_body(v, hashes + offsets[b], offsets[b + 1] - offsets[b], model,
                    filter, has_filter, weights, num_pods, W, epoch, n_tiers,
-                   scores);
+                   ScoreStore{scores});
+}
+
+// k_fused_score with the pick inside: ids / scores [B, top_n] in place of
+// the matrix.  At least 512 B of dynamic LDS (the exchange area).
+__global__ void __launch_bounds__(256) k_fused_topk(
+    Table v, const uint64_t* __restrict__ hashes,
+    const int32_t* __restrict__ offsets,  // [B+1]
+    uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
+    const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
+    int n_tiers, TopkOut out) {
+  const int b = blockIdx.x;
+  fused_score_body(v, hashes + offsets[b], offsets[b + 1] - offsets[b], model,
+                   filter, has_filter, weights, num_pods, W, epoch, n_tiers,
+                   ScoreTopk{out});
 }
 
 // Padded rows: prompt b's keys are hashes[b * stride .. + n_keys[b]).  The
@@ -937,7 +1065,45 @@ __global__ void __launch_bounds__(256) k_fused_score_rows(
     int32_t epoch, int n_tiers, float* __restrict__ scores) {
   const int b = blockIdx.x;
   fused_score_body(v, hashes + (int64_t)b * stride, n_keys[b], model, filter,
-                   has_filter, weights, num_pods, W, epoch, n_tiers, scores);
+                   has_filter, weights, num_pods, W, epoch, n_tiers,
+                   ScoreStore{scores});
+}
+
+__global__ void __launch_bounds__(256) k_fused_topk_rows(
+    Table v, const uint64_t* __restrict__ hashes,  // [B, stride]
+    const int32_t* __restrict__ n_keys,               // [B]
+    int64_t stride, uint32_t model, const uint64_t* __restrict__ filter,
+    int has_filter, const float* __restrict__ weights, int num_pods, int W,
+    int32_t epoch, int n_tiers, TopkOut out) {
+  const int b = blockIdx.x;
+  fused_score_body(v, hashes + (int64_t)b * stride, n_keys[b], model, filter,
+                   has_filter, weights, num_pods, W, epoch, n_tiers,
+                   ScoreTopk{out});
+}
+
+// Top-n of any score matrix [B, P], 1 <= P <= MAX_PODS, values finite and
+// >= 0: the route for what the fused kernel refuses.  One workgroup of 256
+// per row; thread t loads columns t, t + 256, ... (a wave reads 256
+// contiguous bytes per round), PER of them at most, PER a compile-time
+// bound picked on the host so that the keys stay in registers.  A column
+// past P contributes key 0.
+constexpr int TOPK_ROWS_THREADS = 256;
+template <int PER>
+__global__ void __launch_bounds__(TOPK_ROWS_THREADS) k_topk_rows(
+    const float* __restrict__ scores, int P, TopkOut out) {
+  static_assert(PER * TOPK_ROWS_THREADS <= MAX_PODS, "PER is sized by P");
+  __shared__ uint64_t xch[4 * MAX_TOPK];
+  const int64_t b = blockIdx.x;
+  const float* row = scores + b * P;
+  uint64_t key[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int c = i * TOPK_ROWS_THREADS + (int)threadIdx.x;
+    key[i] = c < P ? rank_key(row[c], (uint32_t)c) : 0ull;
+  }
+  const uint64_t mine = wave_topk(key, out.top_n, threadIdx.x & 63);
+  wg_topk_store(mine, xch, out.top_n, out.ids + b * out.top_n,
+                out.scores + b * out.top_n);
 }
 
 // Walk precomputed masks (e.g. after an RCCL all-reduce merge of shard
@@ -1584,8 +1750,39 @@ static bool fused_score_fits(int64_t max_k, int64_t n_tiers, int64_t W) {
   return W <= 16 && fused_score_lds_bytes(max_k, n_tiers, W) <= 64 * 1024;
 }
 
-// One workgroup per prompt.  where...: the kernel arguments between the
-// hashes and the model id, which say where prompt b's keys lie.
+// What a fused launch is shaped by, after the checks every fused op shares.
+struct FusedGeom {
+  int64_t W, n_tiers;
+  size_t lds;  // the masks
+};
+static FusedGeom fused_geom_checked(int64_t num_pods, int64_t max_k,
+                                    int64_t n_tiers) {
+  int64_t W = pod_words(num_pods);
+  TORCH_CHECK(W <= 16, "fused score supports up to 1024 pods");
+  n_tiers = clamp_tiers(n_tiers);
+  TORCH_CHECK(fused_score_fits(max_k, n_tiers, W),
+              "fused score LDS overflow: reduce keys per prompt or pods");
+  return {W, n_tiers, fused_score_lds_bytes(max_k, n_tiers, W)};
+}
+
+// One workgroup per prompt, B >= 1.  out: the kernel's last argument;
+// where...: the kernel arguments between the hashes and the model id,
+// which say where prompt b's keys lie.
+template <typename Kern, typename Out, typename... Where>
+static void launch_fused(Kern kernel, const Table& v, int64_t B,
+                         const FusedGeom& g, size_t lds_bytes,
+                         const at::Tensor& hashes, int64_t model_id,
+                         const at::Tensor& filter_words,
+                         const at::Tensor& weights, int64_t num_pods,
+                         int64_t epoch, Out out, Where... where) {
+  const uint64_t* filter = filter_ptr(filter_words);
+  hipLaunchKernelGGL(kernel, dim3((int)B), dim3(256), lds_bytes, STREAM, v,
+                     (const uint64_t*)u64p(hashes), where...,
+                     (uint32_t)model_id, filter, filter ? 1 : 0,
+                     weights.data_ptr<float>(), (int)num_pods, (int)g.W,
+                     (int32_t)epoch, (int)g.n_tiers, out);
+}
+
 template <typename Kern, typename... Where>
 static at::Tensor launch_fused_score(Kern kernel, const Table& v, int64_t B,
                                      const at::Tensor& hashes,
@@ -1595,21 +1792,58 @@ static at::Tensor launch_fused_score(Kern kernel, const Table& v, int64_t B,
                                      int64_t num_pods, int64_t epoch,
                                      int64_t max_k, int64_t n_tiers,
                                      Where... where) {
-  int64_t W = pod_words(num_pods);
-  TORCH_CHECK(W <= 16, "fused score supports up to 1024 pods");
-  n_tiers = clamp_tiers(n_tiers);
-  TORCH_CHECK(fused_score_fits(max_k, n_tiers, W),
-              "fused score LDS overflow: reduce keys per prompt or pods");
+  const FusedGeom g = fused_geom_checked(num_pods, max_k, n_tiers);
   auto scores = at::zeros({B, num_pods}, hashes.options().dtype(at::kFloat));
   if (B == 0) return scores;
-  const uint64_t* filter = filter_ptr(filter_words);
-  hipLaunchKernelGGL(kernel, dim3((int)B), dim3(256),
-                     fused_score_lds_bytes(max_k, n_tiers, W), STREAM, v,
-                     (const uint64_t*)u64p(hashes), where...,
-                     (uint32_t)model_id, filter, filter ? 1 : 0,
-                     weights.data_ptr<float>(), (int)num_pods, (int)W,
-                     (int32_t)epoch, (int)n_tiers, scores.data_ptr<float>());
+  launch_fused(kernel, v, B, g, g.lds, hashes, model_id, filter_words, weights,
+               num_pods, epoch, scores.data_ptr<float>(), where...);
   return scores;
+}
+
+// {ids int32 [B, top_n], scores float32 [B, top_n]} beside `like`, not
+// filled: the top-n kernels write every slot.
+static constexpr size_t TOPK_XCH_BYTES = 4 * MAX_TOPK * sizeof(uint64_t);
+static std::vector<at::Tensor> topk_alloc(const at::Tensor& like, int64_t B,
+                                          int64_t top_n) {
+  return {at::empty({B, top_n}, like.options().dtype(at::kInt)),
+          at::empty({B, top_n}, like.options().dtype(at::kFloat))};
+}
+static TopkOut topk_out(const std::vector<at::Tensor>& r, int64_t top_n) {
+  return {r[0].data_ptr<int32_t>(), r[1].data_ptr<float>(), (int)top_n};
+}
+
+// launch_fused_score for the top-n entries: the same checks, no fill, and
+// dynamic LDS of at least the exchange area (one key, one tier, 64 pods
+// are 8 bytes of masks).
+template <typename Kern, typename... Where>
+static std::vector<at::Tensor> launch_fused_topk(
+    Kern kernel, const Table& v, int64_t B, const at::Tensor& hashes,
+    int64_t model_id, const at::Tensor& filter_words,
+    const at::Tensor& weights, int64_t num_pods, int64_t epoch, int64_t max_k,
+    int64_t n_tiers, int64_t top_n, Where... where) {
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  const FusedGeom g = fused_geom_checked(num_pods, max_k, n_tiers);
+  auto r = topk_alloc(hashes, B, top_n);
+  if (B == 0) return r;
+  launch_fused(kernel, v, B, g, std::max(g.lds, TOPK_XCH_BYTES), hashes,
+               model_id, filter_words, weights, num_pods, epoch,
+               topk_out(r, top_n), where...);
+  return r;
+}
+
+// The padded rows of the *_rows ops: hashes int64 [B, stride], n_keys
+// int32 [B], both on the device.
+static void check_padded_rows(const at::Tensor& hashes,
+                              const at::Tensor& n_keys, int64_t max_k) {
+  TORCH_CHECK(hashes.is_cuda() && hashes.dtype() == at::kLong &&
+                  hashes.dim() == 2 && hashes.is_contiguous(),
+              "hashes must be a contiguous int64 [B, stride] device tensor");
+  TORCH_CHECK(n_keys.is_cuda() && n_keys.dtype() == at::kInt &&
+                  n_keys.is_contiguous(),
+              "n_keys must be a contiguous int32 device tensor");
+  TORCH_CHECK(n_keys.numel() == hashes.size(0),
+              "n_keys must have one entry per row");
+  TORCH_CHECK(max_k <= hashes.size(1), "max_k exceeds the row length");
 }
 
 // Runs f(std::integral_constant<int, BS>) for a block size the transposed
@@ -1883,19 +2117,58 @@ at::Tensor kvidx::gpu_fused_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                                        int64_t epoch, int64_t max_k,
                                        int64_t n_tiers) {
   auto v = make_table_view(KVIDX_TABLE_ARGS, true);
-  TORCH_CHECK(hashes.is_cuda() && hashes.dtype() == at::kLong &&
-                  hashes.dim() == 2 && hashes.is_contiguous(),
-              "hashes must be a contiguous int64 [B, stride] device tensor");
-  TORCH_CHECK(n_keys.is_cuda() && n_keys.dtype() == at::kInt &&
-                  n_keys.is_contiguous(),
-              "n_keys must be a contiguous int32 device tensor");
-  int64_t B = hashes.size(0);
-  int64_t stride = hashes.size(1);
-  TORCH_CHECK(n_keys.numel() == B, "n_keys must have one entry per row");
-  TORCH_CHECK(max_k <= stride, "max_k exceeds the row length");
-  return launch_fused_score(k_fused_score_rows, v, B, hashes, model_id,
-                            filter_words, weights, num_pods, epoch, max_k,
-                            n_tiers, (const int32_t*)i32p(n_keys), stride);
+  check_padded_rows(hashes, n_keys, max_k);
+  return launch_fused_score(k_fused_score_rows, v, hashes.size(0), hashes,
+                            model_id, filter_words, weights, num_pods, epoch,
+                            max_k, n_tiers, (const int32_t*)i32p(n_keys),
+                            hashes.size(1));
+}
+
+std::vector<at::Tensor> kvidx::gpu_fused_topk(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t max_k, int64_t n_tiers,
+    int64_t top_n) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  return launch_fused_topk(k_fused_topk, v, offsets.numel() - 1, hashes,
+                           model_id, filter_words, weights, num_pods, epoch,
+                           max_k, n_tiers, top_n,
+                           (const int32_t*)i32p(offsets));
+}
+
+std::vector<at::Tensor> kvidx::gpu_fused_topk_rows(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor n_keys, int64_t model_id,
+    at::Tensor filter_words, at::Tensor weights, int64_t num_pods,
+    int64_t epoch, int64_t max_k, int64_t n_tiers, int64_t top_n) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  check_padded_rows(hashes, n_keys, max_k);
+  return launch_fused_topk(k_fused_topk_rows, v, hashes.size(0), hashes,
+                           model_id, filter_words, weights, num_pods, epoch,
+                           max_k, n_tiers, top_n,
+                           (const int32_t*)i32p(n_keys), hashes.size(1));
+}
+
+std::vector<at::Tensor> kvidx::gpu_topk_rows(at::Tensor scores,
+                                             int64_t top_n) {
+  TORCH_CHECK(scores.is_cuda(), "scores must live on the GPU");
+  const int64_t P = topk_rows_checked(scores, top_n);
+  const int64_t B = scores.size(0);
+  TORCH_CHECK(B <= INT32_MAX, "too many rows in one batch");
+  auto r = topk_alloc(scores, B, top_n);
+  if (B == 0) return r;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(TOPK_ROWS_THREADS), 0,
+                       STREAM, (const float*)scores.data_ptr<float>(), (int)P,
+                       topk_out(r, top_n));
+  };
+  // columns per thread: the power of two that covers P
+  const int64_t per = (P + TOPK_ROWS_THREADS - 1) / TOPK_ROWS_THREADS;
+  if (per <= 1) launch(k_topk_rows<1>);
+  else if (per <= 2) launch(k_topk_rows<2>);
+  else if (per <= 4) launch(k_topk_rows<4>);
+  else if (per <= 8) launch(k_topk_rows<8>);
+  else launch(k_topk_rows<16>);
+  return r;
 }
 
 at::Tensor kvidx::gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
@@ -1930,6 +2203,25 @@ at::Tensor kvidx::gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
   auto fm = gpu_lookup(KVIDX_TABLE_ARGS, hashes, model_id, filter_words,
                        num_pods, epoch, 0, 1, n_tiers);
   return gpu_score_from_masks(fm[1].contiguous(), offsets, weights, num_pods);
+}
+
+// gpu_score_hashes' decision with the pick on the device: the matrix only
+// exists on the split route, and never leaves the device there.
+std::vector<at::Tensor> kvidx::gpu_topk_hashes(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t max_k, int64_t n_tiers,
+    int64_t top_n) {
+  if (fused_score_fits(max_k, clamp_tiers(n_tiers), pod_words(num_pods)))
+    return gpu_fused_topk(KVIDX_TABLE_ARGS, hashes, offsets, model_id,
+                          filter_words, weights, num_pods, epoch, max_k,
+                          n_tiers, top_n);
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  auto fm = gpu_lookup(KVIDX_TABLE_ARGS, hashes, model_id, filter_words,
+                       num_pods, epoch, 0, 1, n_tiers);
+  return gpu_topk_rows(
+      gpu_score_from_masks(fm[1].contiguous(), offsets, weights, num_pods),
+      top_n);
 }
 
 std::vector<at::Tensor> kvidx::gpu_hash_chain(
@@ -2035,33 +2327,43 @@ std::vector<at::Tensor> kvidx::gpu_stage_ragged_tokens(
 // host wait in between.  Returns float32 [B, num_pods] on the table's
 // device.  Scores equal hash_chain_batch + gpu_fused_score bit for bit:
 // same chain function, same walk.
-at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
-                                        at::Tensor tokens_flat,
-                                        at::Tensor offsets, int64_t model_id,
-                                        at::Tensor filter_words,
-                                        at::Tensor weights, int64_t num_pods,
-                                        int64_t epoch, int64_t init_hash_bits,
-                                        int64_t block_size, int64_t n_tiers,
-                                        int64_t algo) {
+//
+// Both ops over flat tokens are these two steps and a last call.
+// chain_flat_tokens: stage -> chain; rows int64 [B, max_k] and n_keys int32
+// [B] on the table's device (undefined where B or max_k is 0).
+namespace kvidx {
+struct ChainedRows {
+  RaggedPlan p;
+  at::Tensor rows, n_keys;
+};
+static ChainedRows chain_flat_tokens(const at::Tensor& keys,
+                                     const at::Tensor& tokens_flat,
+                                     const at::Tensor& offsets,
+                                     int64_t init_hash_bits,
+                                     int64_t block_size, int64_t algo) {
   TORCH_CHECK(keys.is_cuda(), "table must live on the GPU");
   TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
-  auto p = plan_ragged(tokens_flat, offsets, block_size);
+  ChainedRows c;
+  c.p = plan_ragged(tokens_flat, offsets, block_size);
+  if (c.p.B == 0 || c.p.max_k == 0) return c;
   auto dev = keys.device();
-  auto fopt = at::TensorOptions().device(dev).dtype(at::kFloat);
-  if (p.B == 0 || p.max_k == 0) return at::zeros({p.B, num_pods}, fopt);
-  auto staged = stage_ragged(p, tokens_flat, block_size, dev);
-  auto parents = at::full({p.B}, init_hash_bits, fopt.dtype(at::kLong));
-  auto hashes = gpu_hash_chain_tr(staged[0], parents, staged[1], block_size,
-                                  p.max_k, 0, 1, algo);
-  if (fused_score_fits(p.max_k, clamp_tiers(n_tiers), pod_words(num_pods)))
-    return gpu_fused_score_rows(KVIDX_TABLE_ARGS, hashes, staged[1], model_id,
-                                filter_words, weights, num_pods, epoch,
-                                p.max_k, n_tiers);
-  // The masks do not fit in LDS: gather the live slots of the rows into
-  // flat hashes for gpu_score_hashes.  It asks fused_score_fits the same
-  // question again, so from here its fused branch is never taken: this
-  // is the two-kernel path.  The gather index comes from the host's
-  // n_chunks, no wait.
+  auto staged = stage_ragged(c.p, tokens_flat, block_size, dev);
+  auto parents = at::full({c.p.B}, init_hash_bits,
+                          at::TensorOptions().device(dev).dtype(at::kLong));
+  c.n_keys = staged[1];
+  c.rows = kvidx::gpu_hash_chain_tr(staged[0], parents, staged[1], block_size,
+                                    c.p.max_k, 0, 1, algo);
+  return c;
+}
+
+// Where the masks do not fit in LDS: the live slots of the rows gathered
+// into {flat hashes, offsets int32 [B+1]} for gpu_score_hashes or
+// gpu_topk_hashes.  Those ask fused_score_fits the same question again, so
+// from here their fused branch is never taken: this is the two-kernel
+// path.  The gather index comes from the host's n_chunks, no wait.
+static std::vector<at::Tensor> gather_live_slots(const ChainedRows& c) {
+  const RaggedPlan& p = c.p;
+  auto dev = c.rows.device();
   auto idx_h = at::empty({p.total_chunks}, at::kLong);
   auto off_h = at::empty({p.B + 1}, at::kInt);
   {
@@ -2076,10 +2378,55 @@ at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
     }
     op[p.B] = (int32_t)n;
   }
-  auto flat = hashes.view({-1}).index_select(0, idx_h.to(dev));
-  return gpu_score_hashes(KVIDX_TABLE_ARGS, flat, off_h.to(dev), model_id,
+  return {c.rows.view({-1}).index_select(0, idx_h.to(dev)), off_h.to(dev)};
+}
+}  // namespace kvidx
+
+at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
+                                        at::Tensor tokens_flat,
+                                        at::Tensor offsets, int64_t model_id,
+                                        at::Tensor filter_words,
+                                        at::Tensor weights, int64_t num_pods,
+                                        int64_t epoch, int64_t init_hash_bits,
+                                        int64_t block_size, int64_t n_tiers,
+                                        int64_t algo) {
+  auto c = chain_flat_tokens(keys, tokens_flat, offsets, init_hash_bits,
+                             block_size, algo);
+  const RaggedPlan& p = c.p;
+  if (p.B == 0 || p.max_k == 0)
+    return at::zeros({p.B, num_pods}, keys.options().dtype(at::kFloat));
+  if (fused_score_fits(p.max_k, clamp_tiers(n_tiers), pod_words(num_pods)))
+    return gpu_fused_score_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
+                                filter_words, weights, num_pods, epoch,
+                                p.max_k, n_tiers);
+  auto flat = gather_live_slots(c);
+  return gpu_score_hashes(KVIDX_TABLE_ARGS, flat[0], flat[1], model_id,
                           filter_words, weights, num_pods, epoch, p.max_k,
                           n_tiers);
+}
+
+// gpu_score_flat_tokens with top-n as the last call.  A batch without a
+// whole chunk has no candidates: (-1, 0.0f) everywhere, no launch.
+std::vector<at::Tensor> kvidx::gpu_topk_flat_tokens(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
+    int64_t block_size, int64_t n_tiers, int64_t algo, int64_t top_n) {
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  auto c = chain_flat_tokens(keys, tokens_flat, offsets, init_hash_bits,
+                             block_size, algo);
+  const RaggedPlan& p = c.p;
+  if (p.B == 0 || p.max_k == 0)
+    return {at::full({p.B, top_n}, -1, keys.options().dtype(at::kInt)),
+            at::zeros({p.B, top_n}, keys.options().dtype(at::kFloat))};
+  if (fused_score_fits(p.max_k, clamp_tiers(n_tiers), pod_words(num_pods)))
+    return gpu_fused_topk_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
+                               filter_words, weights, num_pods, epoch, p.max_k,
+                               n_tiers, top_n);
+  auto flat = gather_live_slots(c);
+  return gpu_topk_hashes(KVIDX_TABLE_ARGS, flat[0], flat[1], model_id,
+                         filter_words, weights, num_pods, epoch, p.max_k,
+                         n_tiers, top_n);
 }
 
 void kvidx::gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,

@@ -794,6 +794,33 @@ inline void pod_census_host(const Table& v, int64_t model_id, int num_pods,
   *sum = s;
 }
 
+// ---- score top-n ------------------------------------------------------
+// The best top_n pods of a prompt, 1 <= top_n <= MAX_TOPK, from its scores
+// (finite, >= 0).  Only pods with score > 0 take part; result r is the pod
+// with the r-th largest score, equal scores in ascending pod id; unused
+// result slots hold id -1 and score 0.0f.  Host and device rank through
+// one 64-bit key: the score's bit pattern (which orders like the number
+// for finite values >= 0) above the complemented pod id, so that keys of
+// different pods are never equal and a plain unsigned maximum is the
+// whole ordering.  A key below RANK_KEY_MIN is "score 0, not a candidate".
+static constexpr int MAX_TOPK = 16;
+static constexpr uint64_t RANK_KEY_MIN = 1ull << 32;
+
+KVIDX_HD uint64_t rank_key(float score, uint32_t pid) {
+  uint32_t bits;
+  __builtin_memcpy(&bits, &score, sizeof bits);
+  return ((uint64_t)bits << 32) | (0xFFFFFFFFu - pid);
+}
+KVIDX_HD int32_t rank_key_id(uint64_t key) {
+  return key < RANK_KEY_MIN ? -1 : (int32_t)(0xFFFFFFFFu - (uint32_t)key);
+}
+KVIDX_HD float rank_key_score(uint64_t key) {
+  const uint32_t bits = (uint32_t)(key >> 32);  // 0 below RANK_KEY_MIN
+  float score;
+  __builtin_memcpy(&score, &bits, sizeof score);
+  return score;
+}
+
 // Sharding: the main table holds only the keys a shard owns (the engine
 // map is replicated on every shard).
 KVIDX_HD bool owns_key(uint64_t h, int shard_id, int num_shards) {

@@ -82,6 +82,12 @@ at::Tensor cpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
 std::vector<at::Tensor> cpu_get_request_keys(KVIDX_TABLE_PARAMS,
                                              at::Tensor engine_hashes,
                                              int64_t model_id);
+// Score top-n (the ordering contract: kvidx_common.h rank_key): scores
+// float32 [B, P] on the host, 1 <= P <= MAX_PODS, finite and >= 0.
+// -> {ids int32 [B, top_n], scores float32 [B, top_n]}.  What the CPU table
+// serves top-n with (cpu_fused_score, then this), and the host statement
+// of the contract the GPU ops are tested against.
+std::vector<at::Tensor> cpu_score_topk(at::Tensor scores, int64_t top_n);
 
 #ifdef KVIDX_WITH_HIP
 // ---- table and chain ops, gfx950 (hip_ops.hip) -----------------------
@@ -130,6 +136,32 @@ at::Tensor gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                             at::Tensor filter_words, at::Tensor weights,
                             int64_t num_pods, int64_t epoch, int64_t max_k,
                             int64_t n_tiers);
+// Score top-n on the device: every op returns {ids int32 [B, top_n],
+// scores float32 [B, top_n]} in the kvidx_common.h rank_key order, written
+// by the kernels in full (no fill).  gpu_fused_topk[_rows] take what
+// gpu_fused_score[_rows] take and pick inside the walk kernel, so the
+// [B, num_pods] matrix never exists; they refuse what fused_score_fits
+// refuses.  gpu_topk_rows takes any float32 [B, P] device matrix, 1 <= P
+// <= MAX_PODS, values finite and >= 0.  gpu_topk_hashes is the chooser
+// (gpu_score_hashes' decision): the fused kernel where it fits, else
+// gpu_lookup + gpu_score_from_masks + gpu_topk_rows.
+std::vector<at::Tensor> gpu_fused_topk(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                       at::Tensor offsets, int64_t model_id,
+                                       at::Tensor filter_words,
+                                       at::Tensor weights, int64_t num_pods,
+                                       int64_t epoch, int64_t max_k,
+                                       int64_t n_tiers, int64_t top_n);
+std::vector<at::Tensor> gpu_fused_topk_rows(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor n_keys, int64_t model_id,
+    at::Tensor filter_words, at::Tensor weights, int64_t num_pods,
+    int64_t epoch, int64_t max_k, int64_t n_tiers, int64_t top_n);
+std::vector<at::Tensor> gpu_topk_rows(at::Tensor scores, int64_t top_n);
+std::vector<at::Tensor> gpu_topk_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                        at::Tensor offsets, int64_t model_id,
+                                        at::Tensor filter_words,
+                                        at::Tensor weights, int64_t num_pods,
+                                        int64_t epoch, int64_t max_k,
+                                        int64_t n_tiers, int64_t top_n);
 std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
                                        at::Tensor parents, int64_t block_size,
                                        int64_t algo);
@@ -147,6 +179,15 @@ at::Tensor gpu_score_flat_tokens(KVIDX_TABLE_PARAMS, at::Tensor tokens_flat,
                                  int64_t num_pods, int64_t epoch,
                                  int64_t init_hash_bits, int64_t block_size,
                                  int64_t n_tiers, int64_t algo);
+// gpu_score_flat_tokens with the pick on the device as well: stage, chain
+// (row-major) and the fused top-n over the rows on one stream, no host
+// wait in between; where the rows do not fit, the gather route followed by
+// gpu_topk_hashes.
+std::vector<at::Tensor> gpu_topk_flat_tokens(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
+    int64_t block_size, int64_t n_tiers, int64_t algo, int64_t top_n);
 void gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,
                       at::Tensor tok_off, at::Tensor ehashes,
                       at::Tensor eh_off, at::Tensor parents,
@@ -261,6 +302,19 @@ inline int64_t census_bins_checked(KVIDX_TABLE_PARAMS, int64_t model_id,
   TORCH_CHECK(meta.numel() == keys.numel() && e_meta.numel() == keys.numel(),
               "meta and e_meta must hold capacity words");
   return num_pods * n_tiers;
+}
+
+// Pod columns P of a score matrix, after the checks cpu_score_topk and
+// gpu_topk_rows share.
+inline int64_t topk_rows_checked(const at::Tensor& scores, int64_t top_n) {
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  TORCH_CHECK(scores.dtype() == at::kFloat && scores.dim() == 2 &&
+                  scores.is_contiguous(),
+              "scores must be a contiguous float32 [B, P] tensor");
+  const int64_t P = scores.size(1);
+  TORCH_CHECK(P >= 1 && P <= MAX_PODS, "scores must have 1..", MAX_PODS,
+              " pod columns");
+  return P;
 }
 
 // Runs f(std::integral_constant<int, ALGO>) for a native chain algo id

@@ -97,15 +97,20 @@ class AsgiIndexerApp:
         prompts = body.get("prompts")
         if not isinstance(prompts, list) or not prompts:
             raise _BadRequest("field 'prompts' (non-empty list) required")
+        from .http_server import parse_top_k, score_batch_payload
+
+        try:
+            top_k = parse_top_k(body)  # optional: {"top": ...} answer
+        except ValueError as e:
+            raise _BadRequest(str(e))
         model = body.get("model", "")
         pool = self.indexer.tokenizers_pool
         if hasattr(pool, "tokenize_batch"):
             token_lists = pool.tokenize_batch(list(prompts), model)
         else:
             token_lists = [pool.tokenize(None, p, model) for p in prompts]
-        scores = self.indexer.score_tokens_batch(
-            token_lists, model, body.get("pods", []))
-        await self._json(send, 200, {"scores": scores})
+        await self._json(send, 200, score_batch_payload(
+            self.indexer, token_lists, model, body.get("pods", []), top_k))
 
     async def _score_chat(self, send, body: Dict[str, Any]):
         model = body.get("model", "")

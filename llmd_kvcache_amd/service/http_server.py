@@ -4,6 +4,10 @@
  - POST /score_completions        {"prompt", "model"} -> {pod: score}
  - POST /score_batch              {"prompts": [...], "model"} ->
                                   {"scores": [{pod: score}, ...]}  (one fused kernel)
+                                  with "top_k": n (integer 1..16, else 400) ->
+                                  {"top": [[[pod, score], ...], ...]}: each
+                                  prompt's n best pods, best first, picked
+                                  on the table's device
  - POST /score_chat_completions   chat-completions request -> {"podScores",
    "templated_messages"}  (template fetched for the model when absent)
  - GET  /metrics                  Prometheus exposition
@@ -80,6 +84,28 @@ def parse_census_query(query: str) -> Optional[str]:
     """Query string of GET /pods/census -> the model name, or None (every
     model) when there is no non-empty "model" parameter."""
     return (parse_qs(query).get("model") or [None])[0] or None
+
+
+def parse_top_k(req) -> Optional[int]:
+    """The optional "top_k" field of POST /score_batch: None when absent,
+    else an integer in 1..16 (ValueError otherwise; the fronts answer
+    400)."""
+    if "top_k" not in req:
+        return None
+    from ..kvblock.gpu_index import check_top_n
+
+    return check_top_n(req["top_k"])
+
+
+def score_batch_payload(indexer: Indexer, token_lists, model, pods,
+                        top_k: Optional[int]):
+    """Answer of POST /score_batch: {"scores": [{pod: score}, ...]}, or
+    with top_k {"top": [[[pod, score], ...], ...]}."""
+    if top_k is None:
+        return {"scores": indexer.score_tokens_batch(token_lists, model,
+                                                     pods)}
+    return {"top": indexer.top_pods_tokens_batch(token_lists, model, pods,
+                                                 top_k)}
 
 
 def make_handler(indexer: Indexer, coalescer=None):
@@ -184,15 +210,19 @@ def make_handler(indexer: Indexer, coalescer=None):
                 self._send_error(400, "field 'prompts' (non-empty list) "
                                       "required")
                 return
+            try:
+                top_k = parse_top_k(req)
+            except ValueError as e:
+                self._send_error(400, str(e))
+                return
             pool = indexer.tokenizers_pool
             if hasattr(pool, "tokenize_batch"):
                 token_lists = pool.tokenize_batch(list(prompts), model)
             else:
                 token_lists = [pool.tokenize(None, p, model)
                                for p in prompts]
-            scores = indexer.score_tokens_batch(
-                token_lists, model, req.get("pods", []))
-            self._send_json(200, {"scores": scores})
+            self._send_json(200, score_batch_payload(
+                indexer, token_lists, model, req.get("pods", []), top_k))
 
         def _pods_purge(self, remove: bool):
             req = self._read_json()
