@@ -372,9 +372,11 @@ class KvTable:
     def score_hashes(self, hashes, counts_or_offsets, model_id, filter_words,
                      weights, num_pods, max_k=None, n_tiers=MAX_TIERS):
         if self.is_cuda:
-            # fused kernel, or lookup + mask walk where its LDS is too
-            # small.  n_tiers (tiers registered) sizes that LDS: 1-2 tiers
-            # keep 256-pod fleets at 16-32 KB/WG and full occupancy.
+            # resident fused kernel, or the tiled one (keys through LDS a
+            # tile at a time, one launch, no global masks) where a
+            # prompt's masks pass 64 KB or the fleet 1024 pods.  n_tiers
+            # (tiers registered) sizes that LDS: 1-2 tiers keep 256-pod
+            # fleets at 16-32 KB/WG and full occupancy.
             return self.ops.gpu_score_hashes(
                 *self._t(), hashes, counts_or_offsets, model_id, filter_words,
                 weights, num_pods, self.next_epoch(),
@@ -388,9 +390,10 @@ class KvTable:
         """score_hashes with each prompt's best top_n pods picked where
         the scores are: (ids int32, scores float32), both [B, top_n], in
         the rank_key order of kvidx_common.h ((-1, 0.0) where fewer pods
-        score).  On a GPU table inside the fused kernel, or by
-        k_topk_rows behind the split route; on a CPU table by
-        cpu_score_topk over the matrix."""
+        score).  On a GPU table inside the resident fused kernel, or
+        inside the tiled one where the masks do not fit its LDS (up to
+        4096 pods, any prompt length); on a CPU table by cpu_score_topk
+        over the matrix."""
         if self.is_cuda:
             ids, top = self.ops.gpu_topk_hashes(
                 *self._t(), hashes, counts_or_offsets, model_id, filter_words,

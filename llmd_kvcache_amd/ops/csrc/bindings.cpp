@@ -76,6 +76,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_topk_rows", &kvidx::gpu_topk_rows, py::arg("scores"),
         py::arg("top_n"));
   m.def("gpu_topk_hashes", &kvidx::gpu_topk_hashes);
+  // the fused ops for any prompt length and fleet: keys tiled through LDS
+  m.def("tiled_score_tile_keys", &kvidx::tiled_score_tile_keys,
+        py::arg("n_tiers"), py::arg("W"));
+  m.def("gpu_tiled_score", &kvidx::gpu_tiled_score);
+  m.def("gpu_tiled_score_rows", &kvidx::gpu_tiled_score_rows);
+  m.def("gpu_tiled_topk", &kvidx::gpu_tiled_topk);
+  m.def("gpu_tiled_topk_rows", &kvidx::gpu_tiled_topk_rows);
   // stage + chain + top-n in one call; the GIL is released for all of it
   m.def("gpu_topk_flat_tokens", &kvidx::gpu_topk_flat_tokens,
         py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),

@@ -300,6 +300,14 @@ DEV int dev_probe_collect(const Table& v, uint64_t h, uint32_t model,
   return any_raw ? 1 : 2;
 }
 
+// dev_probe_collect for a key whose pods can no longer score: the find and
+// the LRU touch, no pod row read, no mask.
+DEV void dev_probe_touch(const Table& v, uint64_t h, uint32_t model,
+                         int32_t epoch) {
+  int64_t slot = dev_table_find(v, h, model);
+  if (slot >= 0) v.stamp[slot] = epoch;
+}
+
 // ---------------------------------------------------------------------
 // Kernels
 // ---------------------------------------------------------------------
@@ -1081,6 +1089,203 @@ __global__ void __launch_bounds__(256) k_fused_topk_rows(
                    ScoreTopk{out});
 }
 
+// ---- tiled fused score: any K, any W <= 64, one launch -----------------
+// fused_score_body keeps all K keys' masks in LDS, which bounds K and W.
+// Nothing in the scoring needs that: the walk is sequential in k and
+// carries an active bit and a score per pod.  Here that state stays in
+// registers for the whole prompt and the keys pass through LDS KT at a
+// time, in two tile buffers [KT, n_tiers, W] (KT: tiled_score_tile_keys on
+// the host), followed by two vote words.
+//
+// Work split: one workgroup of 256 per prompt; wave v owns words v, v + 4,
+// ..., WPW = ceil(W / 4) of them at most, a compile-time bound picked on
+// the host so that score[] / active[] are only indexed by unrolled
+// constants; a word past W is skipped wave-uniformly.  Lane l owns pod
+// bit l.
+//
+// Step i = -1 .. n_tiles - 1, two barriers each:
+//   A  zero the buffer of tile i + 1 (all threads) | barrier
+//   B  probe tile i + 1 into it: key j of the tile by lane j / 4 of wave
+//      j % 4, so every wave has probes in flight; then walk tile i from
+//      the other buffer, which step i - 1 probed | barrier
+// A wave that is through with its probes walks while the others' probes
+// are still in flight, and a wave without a live word only probes.
+//
+// After the break: a word whose active set emptied is never walked again
+// (live, a wave-uniform bit per word).  Each wave that still has a live
+// word after tile i says so in vote word i & 1 before barrier B; if none
+// did, nothing can score any more and the workgroup leaves the loop.  Tile
+// i + 1 is probed by then; the keys from (i + 2) * KT on are found and
+// stamped by dev_probe_touch, 256 at a time, no LDS, no barrier - stamp
+// ends as the split route leaves it.
+//
+// Scores are bit-identical to fused_score_body's and cpu_fused_score's:
+// the same dev_probe_collect and score_walk_step, per pod in key order.
+
+// Epilogues over a lane's WPW final scores; both run behind the loop's
+// last barrier, after which nobody reads masks.
+template <int WPW>
+DEV void tiled_finish(ScoreStore out, int b, const float (&score)[WPW], int W,
+                      int num_pods, unsigned long long*) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < WPW; ++j) {
+    const int w = wave + 4 * j;
+    if (w < W) out.word(b, w * 64 + lane, num_pods, score[j]);
+  }
+}
+
+// One rank key per word, straight into wave_topk<WPW>; the exchange area
+// overlays the front of tile buffer 0.
+template <int WPW>
+DEV void tiled_finish(TopkOut out, int b, const float (&score)[WPW], int W,
+                      int num_pods, unsigned long long* lds) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  uint64_t key[WPW];
+#pragma unroll
+  for (int j = 0; j < WPW; ++j) {
+    const int pid = (wave + 4 * j) * 64 + lane;
+    key[j] = (wave + 4 * j < W && pid < num_pods)
+                 ? rank_key(score[j], (uint32_t)pid)
+                 : 0ull;
+  }
+  const uint64_t mine = wave_topk(key, out.top_n, lane);
+  wg_topk_store(mine, reinterpret_cast<uint64_t*>(lds), out.top_n,
+                out.ids + (size_t)b * out.top_n,
+                out.scores + (size_t)b * out.top_n);
+}
+
+template <int WPW, typename Out>
+DEV void tiled_score_body(
+    Table v, const uint64_t* __restrict__ h, const int K, uint32_t model,
+    const uint64_t* __restrict__ filter, int has_filter,
+    const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
+    int n_tiers, int KT, Out out) {
+  extern __shared__ unsigned long long lds_masks[];  // 2 x [KT, n_tiers, W]
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  // scalar, so that word indices and the live bits are wave-uniform to
+  // the compiler as well
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int TW = n_tiers * W;
+  const int tile_words = KT * TW;
+  int* vote = reinterpret_cast<int*>(lds_masks + 2 * tile_words);  // [2]
+  const int n_tiles = (K + KT - 1) / KT;
+
+  float score[WPW];
+  int active[WPW];
+  unsigned live = 0;  // bit j: word wave + 4 j can still score
+#pragma unroll
+  for (int j = 0; j < WPW; ++j) {
+    score[j] = 0.f;
+    active[j] = 0;
+    if (wave + 4 * j < W) live |= 1u << j;
+  }
+
+  int k_touch = K;  // first key of the touch-only tail
+  for (int i = -1; i < n_tiles; ++i) {
+    // A: the next tile's buffer, and this step's vote word
+    const int nk0 = (i + 1) * KT;
+    const int nlen = min(KT, K - nk0);  // <= 0: there is no next tile
+    unsigned long long* nbuf = lds_masks + ((i + 1) & 1) * tile_words;
+    for (int x = threadIdx.x; x < nlen * TW; x += blockDim.x) nbuf[x] = 0;
+    if (threadIdx.x == 0) vote[i & 1] = 0;
+    __syncthreads();
+
+    // B: the next tile's probes, then this tile's walk
+    const int j = lane * 4 + wave;
+    if (j < nlen)
+      dev_probe_collect(v, h[nk0 + j], model, filter, has_filter, num_pods, W,
+                        epoch, nbuf + (size_t)j * TW, n_tiers);
+    if (i >= 0) {
+      const int k0 = i * KT;
+      const int len = min(KT, K - k0);
+      const unsigned long long* cbuf = lds_masks + (i & 1) * tile_words;
+#pragma unroll
+      for (int jw = 0; jw < WPW; ++jw) {
+        if (!((live >> jw) & 1)) continue;  // past W, or its set is empty
+        const int w = wave + 4 * jw;
+        for (int kk = 0; kk < len; ++kk) {
+          const int act =
+              score_walk_step(cbuf + (size_t)kk * TW + w, W, n_tiers, weights,
+                              lane, k0 + kk == 0, active[jw], score[jw]);
+          if (!__any(act)) {
+            live &= ~(1u << jw);
+            break;
+          }
+        }
+      }
+      if (live && lane == 0) vote[i & 1] = 1;
+    }
+    __syncthreads();
+    if (i >= 0 && !vote[i & 1]) {
+      k_touch = (i + 2) * KT;
+      break;
+    }
+  }
+  for (int64_t k = (int64_t)k_touch + threadIdx.x; k < K; k += blockDim.x)
+    dev_probe_touch(v, h[k], model, epoch);
+
+  tiled_finish<WPW>(out, b, score, W, num_pods, lds_masks);
+}
+
+// The four entries: where prompt b's keys lie (flat hashes with offsets, or
+// padded rows) x what leaves (the matrix, or top-n), as the resident fused
+// kernels above.  Dynamic LDS: tiled_score_lds_bytes on the host.
+template <int WPW>
+__global__ void __launch_bounds__(256) k_tiled_score(
+    Table v, const uint64_t* __restrict__ hashes,
+    const int32_t* __restrict__ offsets,  // [B+1]
+    uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
+    const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
+    int n_tiers, int KT, float* __restrict__ scores) {
+  const int b = blockIdx.x;
+  tiled_score_body<WPW>(v, hashes + offsets[b], offsets[b + 1] - offsets[b],
+                        model, filter, has_filter, weights, num_pods, W, epoch,
+                        n_tiers, KT, ScoreStore{scores});
+}
+
+template <int WPW>
+__global__ void __launch_bounds__(256) k_tiled_topk(
+    Table v, const uint64_t* __restrict__ hashes,
+    const int32_t* __restrict__ offsets,  // [B+1]
+    uint32_t model, const uint64_t* __restrict__ filter, int has_filter,
+    const float* __restrict__ weights, int num_pods, int W, int32_t epoch,
+    int n_tiers, int KT, TopkOut out) {
+  const int b = blockIdx.x;
+  tiled_score_body<WPW>(v, hashes + offsets[b], offsets[b + 1] - offsets[b],
+                        model, filter, has_filter, weights, num_pods, W, epoch,
+                        n_tiers, KT, out);
+}
+
+template <int WPW>
+__global__ void __launch_bounds__(256) k_tiled_score_rows(
+    Table v, const uint64_t* __restrict__ hashes,  // [B, stride]
+    const int32_t* __restrict__ n_keys,               // [B]
+    int64_t stride, uint32_t model, const uint64_t* __restrict__ filter,
+    int has_filter, const float* __restrict__ weights, int num_pods, int W,
+    int32_t epoch, int n_tiers, int KT, float* __restrict__ scores) {
+  const int b = blockIdx.x;
+  tiled_score_body<WPW>(v, hashes + (int64_t)b * stride, n_keys[b], model,
+                        filter, has_filter, weights, num_pods, W, epoch,
+                        n_tiers, KT, ScoreStore{scores});
+}
+
+template <int WPW>
+__global__ void __launch_bounds__(256) k_tiled_topk_rows(
+    Table v, const uint64_t* __restrict__ hashes,  // [B, stride]
+    const int32_t* __restrict__ n_keys,               // [B]
+    int64_t stride, uint32_t model, const uint64_t* __restrict__ filter,
+    int has_filter, const float* __restrict__ weights, int num_pods, int W,
+    int32_t epoch, int n_tiers, int KT, TopkOut out) {
+  const int b = blockIdx.x;
+  tiled_score_body<WPW>(v, hashes + (int64_t)b * stride, n_keys[b], model,
+                        filter, has_filter, weights, num_pods, W, epoch,
+                        n_tiers, KT, out);
+}
+
 // Top-n of any score matrix [B, P], 1 <= P <= MAX_PODS, values finite and
 // >= 0: the route for what the fused kernel refuses.  One workgroup of 256
 // per row; thread t loads columns t, t + 256, ... (a wave reads 256
@@ -1831,6 +2036,110 @@ static std::vector<at::Tensor> launch_fused_topk(
   return r;
 }
 
+// ---- tiled fused score: the launch ---------------------------------------
+// Keys per tile for (n_tiers, W): two buffers of KT keys and the two vote
+// words stay within the 64 KB of dynamic LDS a launch gets without a
+// function attribute.  Up to 256 keys (one probe per thread and tile);
+// past 32 KB a workgroup gives LDS back for residency (four workgroups per
+// CU keep more probes in flight than two with longer tiles), down to 16
+// keys, below which a tile is mostly barriers.
+static constexpr int64_t TILED_VOTE_BYTES = 2 * sizeof(int);
+int64_t tiled_score_tile_keys(int64_t n_tiers, int64_t W) {
+  const int64_t key_bytes = clamp_tiers(n_tiers) * W * sizeof(uint64_t);
+  TORCH_CHECK(W >= 1 && W <= MAX_PODS / 64, "W must be 1..", MAX_PODS / 64);
+  const int64_t fit = (64 * 1024 - TILED_VOTE_BYTES) / (2 * key_bytes);
+  const int64_t kt = std::max<int64_t>(16, 32 * 1024 / (2 * key_bytes));
+  return std::min<int64_t>({256, kt, fit});
+}
+
+// What a tiled launch is shaped by, after the checks every tiled op shares.
+struct TiledGeom {
+  int64_t W, n_tiers, KT;
+  size_t lds;  // both buffers and the vote words
+};
+static TiledGeom tiled_geom_checked(int64_t num_pods, int64_t max_k,
+                                    int64_t n_tiers) {
+  TORCH_CHECK(num_pods >= 1 && num_pods <= MAX_PODS, "num_pods must be 1..",
+              MAX_PODS);
+  TORCH_CHECK(max_k >= 0, "max_k must not be negative");
+  const int64_t W = pod_words(num_pods);
+  n_tiers = clamp_tiers(n_tiers);
+  const int64_t KT = tiled_score_tile_keys(n_tiers, W);
+  const size_t buf = (size_t)KT * n_tiers * W * sizeof(uint64_t);
+  // the top-n exchange area overlays one buffer
+  TORCH_CHECK(buf >= TOPK_XCH_BYTES &&
+                  2 * buf + TILED_VOTE_BYTES <= (size_t)64 * 1024,
+              "tiled score tile out of range");
+  return {W, n_tiers, KT, 2 * buf + TILED_VOTE_BYTES};
+}
+
+// Runs f(std::integral_constant<int, WPW>) for the smallest instantiated
+// words-per-wave bound that covers W <= 64.
+template <typename F>
+static void dispatch_tiled_wpw(int64_t W, F&& f) {
+  const int64_t wpw = (W + 3) / 4;
+  if (wpw <= 1) f(std::integral_constant<int, 1>{});
+  else if (wpw <= 2) f(std::integral_constant<int, 2>{});
+  else if (wpw <= 4) f(std::integral_constant<int, 4>{});
+  else if (wpw <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+
+// One workgroup per prompt, B >= 1: launch_fused with the tile length in
+// front of `out`.
+template <typename Kern, typename Out, typename... Where>
+static void launch_tiled(Kern kernel, const Table& v, int64_t B,
+                         const TiledGeom& g, const at::Tensor& hashes,
+                         int64_t model_id, const at::Tensor& filter_words,
+                         const at::Tensor& weights, int64_t num_pods,
+                         int64_t epoch, Out out, Where... where) {
+  const uint64_t* filter = filter_ptr(filter_words);
+  hipLaunchKernelGGL(kernel, dim3((int)B), dim3(256), g.lds, STREAM, v,
+                     (const uint64_t*)u64p(hashes), where...,
+                     (uint32_t)model_id, filter, filter ? 1 : 0,
+                     weights.data_ptr<float>(), (int)num_pods, (int)g.W,
+                     (int32_t)epoch, (int)g.n_tiers, (int)g.KT, out);
+}
+
+// The two tiled ops of each output kind.  Entry: a generic lambda from WPW
+// to the __global__ instantiation (flat or rows).
+template <typename Entry, typename... Where>
+static at::Tensor launch_tiled_score(Entry entry, const Table& v, int64_t B,
+                                     const at::Tensor& hashes,
+                                     int64_t model_id,
+                                     const at::Tensor& filter_words,
+                                     const at::Tensor& weights,
+                                     int64_t num_pods, int64_t epoch,
+                                     int64_t max_k, int64_t n_tiers,
+                                     Where... where) {
+  const TiledGeom g = tiled_geom_checked(num_pods, max_k, n_tiers);
+  // the kernel writes every column of every row
+  auto scores = at::empty({B, num_pods}, hashes.options().dtype(at::kFloat));
+  if (B == 0) return scores;
+  dispatch_tiled_wpw(g.W, [&](auto N) {
+    launch_tiled(entry(N), v, B, g, hashes, model_id, filter_words, weights,
+                 num_pods, epoch, scores.data_ptr<float>(), where...);
+  });
+  return scores;
+}
+
+template <typename Entry, typename... Where>
+static std::vector<at::Tensor> launch_tiled_topk(
+    Entry entry, const Table& v, int64_t B, const at::Tensor& hashes,
+    int64_t model_id, const at::Tensor& filter_words,
+    const at::Tensor& weights, int64_t num_pods, int64_t epoch, int64_t max_k,
+    int64_t n_tiers, int64_t top_n, Where... where) {
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  const TiledGeom g = tiled_geom_checked(num_pods, max_k, n_tiers);
+  auto r = topk_alloc(hashes, B, top_n);
+  if (B == 0) return r;
+  dispatch_tiled_wpw(g.W, [&](auto N) {
+    launch_tiled(entry(N), v, B, g, hashes, model_id, filter_words, weights,
+                 num_pods, epoch, topk_out(r, top_n), where...);
+  });
+  return r;
+}
+
 // The padded rows of the *_rows ops: hashes int64 [B, stride], n_keys
 // int32 [B], both on the device.
 static void check_padded_rows(const at::Tensor& hashes,
@@ -2148,6 +2457,58 @@ std::vector<at::Tensor> kvidx::gpu_fused_topk_rows(
                            (const int32_t*)i32p(n_keys), hashes.size(1));
 }
 
+// The tiled twins of the four fused ops: the same arguments, any max_k >= 0
+// and any fleet up to MAX_PODS, one launch each.
+at::Tensor kvidx::gpu_tiled_score(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                  at::Tensor offsets, int64_t model_id,
+                                  at::Tensor filter_words, at::Tensor weights,
+                                  int64_t num_pods, int64_t epoch,
+                                  int64_t max_k, int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  return launch_tiled_score(
+      [](auto N) { return k_tiled_score<decltype(N)::value>; }, v,
+      offsets.numel() - 1, hashes, model_id, filter_words, weights, num_pods,
+      epoch, max_k, n_tiers, (const int32_t*)i32p(offsets));
+}
+
+at::Tensor kvidx::gpu_tiled_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                       at::Tensor n_keys, int64_t model_id,
+                                       at::Tensor filter_words,
+                                       at::Tensor weights, int64_t num_pods,
+                                       int64_t epoch, int64_t max_k,
+                                       int64_t n_tiers) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  check_padded_rows(hashes, n_keys, max_k);
+  return launch_tiled_score(
+      [](auto N) { return k_tiled_score_rows<decltype(N)::value>; }, v,
+      hashes.size(0), hashes, model_id, filter_words, weights, num_pods, epoch,
+      max_k, n_tiers, (const int32_t*)i32p(n_keys), hashes.size(1));
+}
+
+std::vector<at::Tensor> kvidx::gpu_tiled_topk(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t max_k, int64_t n_tiers,
+    int64_t top_n) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  return launch_tiled_topk(
+      [](auto N) { return k_tiled_topk<decltype(N)::value>; }, v,
+      offsets.numel() - 1, hashes, model_id, filter_words, weights, num_pods,
+      epoch, max_k, n_tiers, top_n, (const int32_t*)i32p(offsets));
+}
+
+std::vector<at::Tensor> kvidx::gpu_tiled_topk_rows(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor n_keys, int64_t model_id,
+    at::Tensor filter_words, at::Tensor weights, int64_t num_pods,
+    int64_t epoch, int64_t max_k, int64_t n_tiers, int64_t top_n) {
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  check_padded_rows(hashes, n_keys, max_k);
+  return launch_tiled_topk(
+      [](auto N) { return k_tiled_topk_rows<decltype(N)::value>; }, v,
+      hashes.size(0), hashes, model_id, filter_words, weights, num_pods, epoch,
+      max_k, n_tiers, top_n, (const int32_t*)i32p(n_keys), hashes.size(1));
+}
+
 std::vector<at::Tensor> kvidx::gpu_topk_rows(at::Tensor scores,
                                              int64_t top_n) {
   TORCH_CHECK(scores.is_cuda(), "scores must live on the GPU");
@@ -2198,15 +2559,15 @@ at::Tensor kvidx::gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
     return gpu_fused_score(KVIDX_TABLE_ARGS, hashes, offsets, model_id,
                            filter_words, weights, num_pods, epoch, max_k,
                            n_tiers);
-  // The masks do not fit in LDS (huge fleet, or long prompts on a large
-  // one; rare): masks in global memory, then the mask walk.
-  auto fm = gpu_lookup(KVIDX_TABLE_ARGS, hashes, model_id, filter_words,
-                       num_pods, epoch, 0, 1, n_tiers);
-  return gpu_score_from_masks(fm[1].contiguous(), offsets, weights, num_pods);
+  // The masks do not fit in LDS (a fleet past 1024 pods, or long prompts
+  // on a large one): the keys go through LDS a tile at a time.
+  return gpu_tiled_score(KVIDX_TABLE_ARGS, hashes, offsets, model_id,
+                         filter_words, weights, num_pods, epoch, max_k,
+                         n_tiers);
 }
 
-// gpu_score_hashes' decision with the pick on the device: the matrix only
-// exists on the split route, and never leaves the device there.
+// gpu_score_hashes' decision with the pick on the device: the matrix
+// never exists.
 std::vector<at::Tensor> kvidx::gpu_topk_hashes(
     KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor offsets,
     int64_t model_id, at::Tensor filter_words, at::Tensor weights,
@@ -2216,12 +2577,9 @@ std::vector<at::Tensor> kvidx::gpu_topk_hashes(
     return gpu_fused_topk(KVIDX_TABLE_ARGS, hashes, offsets, model_id,
                           filter_words, weights, num_pods, epoch, max_k,
                           n_tiers, top_n);
-  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
-  auto fm = gpu_lookup(KVIDX_TABLE_ARGS, hashes, model_id, filter_words,
-                       num_pods, epoch, 0, 1, n_tiers);
-  return gpu_topk_rows(
-      gpu_score_from_masks(fm[1].contiguous(), offsets, weights, num_pods),
-      top_n);
+  return gpu_tiled_topk(KVIDX_TABLE_ARGS, hashes, offsets, model_id,
+                        filter_words, weights, num_pods, epoch, max_k, n_tiers,
+                        top_n);
 }
 
 std::vector<at::Tensor> kvidx::gpu_hash_chain(
@@ -2355,31 +2713,6 @@ static ChainedRows chain_flat_tokens(const at::Tensor& keys,
                                     c.p.max_k, 0, 1, algo);
   return c;
 }
-
-// Where the masks do not fit in LDS: the live slots of the rows gathered
-// into {flat hashes, offsets int32 [B+1]} for gpu_score_hashes or
-// gpu_topk_hashes.  Those ask fused_score_fits the same question again, so
-// from here their fused branch is never taken: this is the two-kernel
-// path.  The gather index comes from the host's n_chunks, no wait.
-static std::vector<at::Tensor> gather_live_slots(const ChainedRows& c) {
-  const RaggedPlan& p = c.p;
-  auto dev = c.rows.device();
-  auto idx_h = at::empty({p.total_chunks}, at::kLong);
-  auto off_h = at::empty({p.B + 1}, at::kInt);
-  {
-    const int32_t* nc = p.host.data_ptr<int32_t>();
-    int64_t* ip = idx_h.data_ptr<int64_t>();
-    int32_t* op = off_h.data_ptr<int32_t>();
-    TORCH_CHECK(p.total_chunks <= INT32_MAX, "too many chunks in one batch");
-    int64_t n = 0;
-    for (int64_t b = 0; b < p.B; ++b) {
-      op[b] = (int32_t)n;
-      for (int64_t k = 0; k < nc[b]; ++k) ip[n++] = b * p.max_k + k;
-    }
-    op[p.B] = (int32_t)n;
-  }
-  return {c.rows.view({-1}).index_select(0, idx_h.to(dev)), off_h.to(dev)};
-}
 }  // namespace kvidx
 
 at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
@@ -2399,10 +2732,9 @@ at::Tensor kvidx::gpu_score_flat_tokens(KVIDX_TABLE_PARAMS,
     return gpu_fused_score_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
                                 filter_words, weights, num_pods, epoch,
                                 p.max_k, n_tiers);
-  auto flat = gather_live_slots(c);
-  return gpu_score_hashes(KVIDX_TABLE_ARGS, flat[0], flat[1], model_id,
-                          filter_words, weights, num_pods, epoch, p.max_k,
-                          n_tiers);
+  return gpu_tiled_score_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
+                              filter_words, weights, num_pods, epoch, p.max_k,
+                              n_tiers);
 }
 
 // gpu_score_flat_tokens with top-n as the last call.  A batch without a
@@ -2423,10 +2755,9 @@ std::vector<at::Tensor> kvidx::gpu_topk_flat_tokens(
     return gpu_fused_topk_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
                                filter_words, weights, num_pods, epoch, p.max_k,
                                n_tiers, top_n);
-  auto flat = gather_live_slots(c);
-  return gpu_topk_hashes(KVIDX_TABLE_ARGS, flat[0], flat[1], model_id,
-                         filter_words, weights, num_pods, epoch, p.max_k,
-                         n_tiers, top_n);
+  return gpu_tiled_topk_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
+                             filter_words, weights, num_pods, epoch, p.max_k,
+                             n_tiers, top_n);
 }
 
 void kvidx::gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,

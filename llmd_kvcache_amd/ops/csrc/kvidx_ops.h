@@ -127,10 +127,10 @@ at::Tensor gpu_fused_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                                 int64_t n_tiers);
 at::Tensor gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
                                 at::Tensor weights, int64_t num_pods);
-// The one place that decides between the fused kernel and lookup + mask
-// walk: gpu_fused_score where its LDS holds the batch, else gpu_lookup
-// (unsharded) + gpu_score_from_masks.  hashes int64 flat, offsets int32
-// [B+1], both on the device.
+// The one place that decides between the resident and the tiled fused
+// kernel: gpu_fused_score where its LDS holds the batch, else
+// gpu_tiled_score.  hashes int64 flat, offsets int32 [B+1], both on the
+// device.
 at::Tensor gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                             at::Tensor offsets, int64_t model_id,
                             at::Tensor filter_words, at::Tensor weights,
@@ -143,8 +143,8 @@ at::Tensor gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
 // [B, num_pods] matrix never exists; they refuse what fused_score_fits
 // refuses.  gpu_topk_rows takes any float32 [B, P] device matrix, 1 <= P
 // <= MAX_PODS, values finite and >= 0.  gpu_topk_hashes is the chooser
-// (gpu_score_hashes' decision): the fused kernel where it fits, else
-// gpu_lookup + gpu_score_from_masks + gpu_topk_rows.
+// (gpu_score_hashes' decision): the resident fused kernel where it fits,
+// else gpu_tiled_topk.
 std::vector<at::Tensor> gpu_fused_topk(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                                        at::Tensor offsets, int64_t model_id,
                                        at::Tensor filter_words,
@@ -162,6 +162,33 @@ std::vector<at::Tensor> gpu_topk_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                                         at::Tensor weights, int64_t num_pods,
                                         int64_t epoch, int64_t max_k,
                                         int64_t n_tiers, int64_t top_n);
+// The tiled fused kernels: what the four gpu_fused_* ops take and return,
+// bit for bit, for any max_k >= 0 and 1 <= num_pods <= MAX_PODS in one
+// launch and without a global mask tensor.  The keys pass through LDS
+// tiled_score_tile_keys(n_tiers, W) at a time (W = pod_words(num_pods));
+// every probed key that is stored gets the call's epoch, as on every other
+// route.
+int64_t tiled_score_tile_keys(int64_t n_tiers, int64_t W);
+at::Tensor gpu_tiled_score(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                           at::Tensor offsets, int64_t model_id,
+                           at::Tensor filter_words, at::Tensor weights,
+                           int64_t num_pods, int64_t epoch, int64_t max_k,
+                           int64_t n_tiers);
+at::Tensor gpu_tiled_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                at::Tensor n_keys, int64_t model_id,
+                                at::Tensor filter_words, at::Tensor weights,
+                                int64_t num_pods, int64_t epoch, int64_t max_k,
+                                int64_t n_tiers);
+std::vector<at::Tensor> gpu_tiled_topk(KVIDX_TABLE_PARAMS, at::Tensor hashes,
+                                       at::Tensor offsets, int64_t model_id,
+                                       at::Tensor filter_words,
+                                       at::Tensor weights, int64_t num_pods,
+                                       int64_t epoch, int64_t max_k,
+                                       int64_t n_tiers, int64_t top_n);
+std::vector<at::Tensor> gpu_tiled_topk_rows(
+    KVIDX_TABLE_PARAMS, at::Tensor hashes, at::Tensor n_keys, int64_t model_id,
+    at::Tensor filter_words, at::Tensor weights, int64_t num_pods,
+    int64_t epoch, int64_t max_k, int64_t n_tiers, int64_t top_n);
 std::vector<at::Tensor> gpu_hash_chain(at::Tensor tokens, at::Tensor tok_off,
                                        at::Tensor parents, int64_t block_size,
                                        int64_t algo);
@@ -181,8 +208,8 @@ at::Tensor gpu_score_flat_tokens(KVIDX_TABLE_PARAMS, at::Tensor tokens_flat,
                                  int64_t n_tiers, int64_t algo);
 // gpu_score_flat_tokens with the pick on the device as well: stage, chain
 // (row-major) and the fused top-n over the rows on one stream, no host
-// wait in between; where the rows do not fit, the gather route followed by
-// gpu_topk_hashes.
+// wait in between; where the rows do not fit the resident kernel, the
+// tiled one over the same rows.
 std::vector<at::Tensor> gpu_topk_flat_tokens(
     KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
     int64_t model_id, at::Tensor filter_words, at::Tensor weights,
