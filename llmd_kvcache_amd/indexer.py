@@ -62,6 +62,13 @@ class Config:
     # exceeds this stays on the CPU chain (one very long prompt among
     # thousands of short ones)
     device_chain_max_image_bytes: int = 1 << 30
+    # layout of the device route's intermediates: "padded" pads token
+    # image and hashes to the batch's longest prompt and obeys the cap
+    # above; "over_cap" does so while the padded image is within the cap
+    # and sends a batch over it through the ragged ops (per-wave images,
+    # CSR hashes) instead of the CPU chain; "ragged" sends every batch of
+    # the device route through them, and the cap does not apply
+    device_chain_layout: str = "padded"
 
 
 _log = get_logger("indexer")
@@ -75,6 +82,7 @@ class ReadRoute:
     n_chunks: List[int]  # whole chunks per prompt
     max_k: int
     image_bytes: int    # padded int32 token image of the device route
+    ragged: bool = False  # device route through the *_ragged ops
 
 
 def plan_read_route(offsets, block_size: int, hash_algo: str,
@@ -84,7 +92,8 @@ def plan_read_route(offsets, block_size: int, hash_algo: str,
     taken only where it is possible (GPU table, native algo, a block size
     the transposed chain kernel has, image under the cap) and wanted
     ("on", or "auto" at or above the threshold); everything else takes
-    the CPU chain."""
+    the CPU chain.  Config.device_chain_layout decides whether the device
+    route is the padded or the ragged one; the ragged one has no cap."""
     off = offsets.tolist() if hasattr(offsets, "tolist") else list(offsets)
     n_chunks = [(int(off[i + 1]) - int(off[i])) // block_size
                 for i in range(len(off) - 1)]
@@ -94,13 +103,17 @@ def plan_read_route(offsets, block_size: int, hash_algo: str,
     mode = config.device_chain
     if mode not in ("auto", "on"):
         return route
+    within_cap = image_bytes <= config.device_chain_max_image_bytes
+    layout = config.device_chain_layout
+    ragged = layout == "ragged" or (layout == "over_cap" and not within_cap)
     if not (table_on_gpu and hash_algo in hashing.NATIVE_ALGO_IDS
             and block_size in DEVICE_CHAIN_BLOCK_SIZES
-            and image_bytes <= config.device_chain_max_image_bytes):
+            and (within_cap or ragged)):
         return route
     if mode == "auto" and sum(n_chunks) < config.device_chain_min_chunks:
         return route
     route.device = True
+    route.ragged = ragged
     return route
 
 
@@ -374,9 +387,14 @@ class Indexer:
                     a.filter_words, a.weights, a.num_pods,
                     idx.table.next_epoch(), init, bs, a.n_tiers,
                     hashing.NATIVE_ALGO_IDS[tp.config.hash_algo])
+            ops = idx.table.ops
             if top_n is None:
-                return idx.table.ops.gpu_score_flat_tokens(*args)
-            return tuple(idx.table.ops.gpu_topk_flat_tokens(*args, top_n))
+                score = (ops.gpu_score_flat_tokens_ragged if route.ragged
+                         else ops.gpu_score_flat_tokens)
+                return score(*args)
+            topk = (ops.gpu_topk_flat_tokens_ragged if route.ragged
+                    else ops.gpu_topk_flat_tokens)
+            return tuple(topk(*args, top_n))
         parents = torch.full((B,), init, dtype=torch.int64)
         hashes, chunk_off = idx.table.ops.hash_chain_batch(
             tokens_flat, offsets, parents, bs,

@@ -21,6 +21,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tokens_to_chunk_hashes_fast", &kvidx::tokens_to_chunk_hashes_fast,
         py::arg("tokens"), py::arg("parent"), py::arg("block_size"),
         py::arg("algo") = 0);
+  m.def("plan_ragged_waves", &kvidx::plan_ragged_waves_op, py::arg("tokens"),
+        py::arg("offsets"), py::arg("block_size"));
   m.def("cpu_insert", &kvidx::cpu_insert);
   m.def("cpu_compact", &kvidx::cpu_compact);
   m.def("cpu_evict", &kvidx::cpu_evict);
@@ -85,6 +87,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_tiled_topk_rows", &kvidx::gpu_tiled_topk_rows);
   // stage + chain + top-n in one call; the GIL is released for all of it
   m.def("gpu_topk_flat_tokens", &kvidx::gpu_topk_flat_tokens,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("offsets"),
+        py::arg("model_id"), py::arg("filter_words"), py::arg("weights"),
+        py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("n_tiers"), py::arg("algo"),
+        py::arg("top_n"), py::call_guard<py::gil_scoped_release>());
+  // the same three over per-wave token images and CSR hashes
+  m.def("gpu_hash_chain_ragged", &kvidx::gpu_hash_chain_ragged,
+        py::arg("tokens_flat"), py::arg("offsets"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("algo") = 0,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("gpu_score_flat_tokens_ragged", &kvidx::gpu_score_flat_tokens_ragged,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("offsets"),
+        py::arg("model_id"), py::arg("filter_words"), py::arg("weights"),
+        py::arg("num_pods"), py::arg("epoch"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("n_tiers"), py::arg("algo") = 0,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("gpu_topk_flat_tokens_ragged", &kvidx::gpu_topk_flat_tokens_ragged,
         py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
         py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
         py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("offsets"),

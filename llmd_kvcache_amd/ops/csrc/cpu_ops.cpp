@@ -233,6 +233,16 @@ std::vector<at::Tensor> kvidx::hash_chain_batch(
   return {out, chunk_off};
 }
 
+std::vector<at::Tensor> kvidx::plan_ragged_waves_op(at::Tensor tokens,
+                                                    at::Tensor offsets,
+                                                    int64_t block_size) {
+  const WavePlan p = plan_ragged_waves(tokens, offsets, block_size);
+  return {p.i32(p.host, p.at_perm(), 64 * p.G),
+          p.i32(p.host, p.at_wave_k(), p.G), p.img_off(p.host),
+          p.i32(p.host, p.at_tile_start(), p.G + 1),
+          p.i32(p.host, p.at_h_off(), p.B + 1)};
+}
+
 // Tombstone compaction (ROADMAP #9): rehash every live entry of `old`
 // into the freshly-zeroed `nw` bundle (optionally a different power-of-
 // two capacity). Stamps (approximate-LRU epochs) and pod rows are

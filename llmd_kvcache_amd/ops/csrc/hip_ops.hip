@@ -1839,6 +1839,197 @@ __global__ void __launch_bounds__(256) k_stage_ragged_tokens(
   }
 }
 
+// ---------------------------------------------------------------------
+// The ragged (wave-tiled) device chain: stage and chain over one token
+// image PER WAVE of 64 prompts (kvidx_ops.h plan_ragged_waves), hashes out
+// in CSR form.  The prompts are sorted by length, so the 64 of a wave are
+// neighbours in length: wave g's image int32 [wave_k[g] * BS][64] is only
+// as tall as its own longest prompt, its chain loop runs wave_k[g] times,
+// and memory is ~4 B per token + 8 B per chunk whatever the batch's length
+// distribution.  The padded kernels above pay max_k of the whole batch for
+// every wave.
+// ---------------------------------------------------------------------
+
+// Wave of staging tile `tile`: the g with tile_start[g] <= tile <
+// tile_start[g + 1].  tile is uniform over the workgroup, so the steps are
+// scalar loads and branches (as dev_group_of_event for one event).
+DEV int dev_wave_of_tile(const int32_t* __restrict__ tile_start, int G,
+                         int tile) {
+  int lo = 0, hi = G - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_start[mid] <= tile) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// k_stage_ragged_tokens' tile transposition (same LDS tile, same
+// unconditional clamped loads) over the per-wave images.  1-D grid, one
+// workgroup per 64-position tile of one wave: tile rows are the wave's 64
+// prompts perm[64 g ..], -1 a row of zeros; output row t of wave g is the
+// one 256 B line at img + img_off[g] + 64 t.  Every slot of every image is
+// written, a zero at and past a prompt's last whole chunk.
+template <typename TokT>
+__global__ void __launch_bounds__(256) k_stage_ragged_waves(
+    const TokT* __restrict__ flat,            // [total]
+    const int32_t* __restrict__ tok_off,      // [B+1]
+    const int32_t* __restrict__ n_chunks,     // [B]
+    const int32_t* __restrict__ perm,         // [64 G]
+    const int32_t* __restrict__ wave_k,       // [G]
+    const int64_t* __restrict__ img_off,      // [G+1]
+    const int32_t* __restrict__ tile_start,   // [G+1]
+    int G, int block_size,
+    int32_t* __restrict__ img) {
+  __shared__ int32_t tile[STAGE_TILE][STAGE_TILE + 1];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = dev_wave_of_tile(tile_start, G, (int)blockIdx.x);
+  const int64_t t0 = (int64_t)((int)blockIdx.x - tile_start[g]) * STAGE_TILE;
+  const int64_t T = (int64_t)wave_k[g] * block_size;  // rows of this image
+  const int32_t* rows = perm + (int64_t)g * 64;
+  constexpr int ROWS = STAGE_TILE / 4;  // tile rows per wave
+  const int64_t pos = t0 + lane;
+  int32_t x[ROWS];
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) {
+    const int p = rows[wave + 4 * i];  // scalar: one prompt per wave and step
+    const int pc = max(p, 0);
+    const int64_t keep = (int64_t)n_chunks[pc] * block_size;
+    const int64_t first = tok_off[pc];
+    const bool ok = p >= 0 && pos < keep;
+    // token 0 exists: a planned wave has a prompt with a whole chunk
+    const int32_t v = (int32_t)flat[ok ? first + pos : 0];
+    x[i] = ok ? v : 0;
+  }
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) tile[wave + 4 * i][lane] = x[i];
+  __syncthreads();
+  int32_t* out = img + img_off[g];
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) {
+    const int r = wave + 4 * i;
+    if (t0 + r < T) out[(t0 + r) * 64 + lane] = tile[lane][r];
+  }
+}
+
+// chain_flush_rows for CSR output: row r of the wave is prompt perm[..+r],
+// whose chunks go to out[h_off + c], c < its n_chunks.  The flushing lane
+// gets both from lane r by shuffle.  CSR has no padding - the slot after a
+// prompt's last chunk is the next prompt's first - so only chunks below
+// n_chunks are stored, and a 16-byte store is taken only for a whole pair
+// whose destination is 16-byte aligned (an even row start; odd rows keep
+// 8-byte stores).  ho / mc: this lane's own h_off and n_chunks (0 chunks
+// for a lane without a prompt).
+DEV void chain_flush_csr(const uint64_t* stage, uint64_t* __restrict__ out,
+                         int ho, int mc, int wl, int c) {
+  const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
+  const int c0 = c - cc;
+  const bool base16 = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int part2 = 2 * (wl & 7);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    const int r = g * 8 + (wl >> 3);
+    const int ho_r = __shfl(ho, r, 64);
+    const int mc_r = __shfl(mc, r, 64);
+    const uint64_t* s = stage + r * CHAIN_STAGE_ROW + part2;
+    const uint64_t v0 = s[0];
+    const uint64_t v1 = s[1];
+    // chunks c0 + part2, + 1 of row r; what is staged ends at c <= its
+    // wave's last chunk, so "below mc_r" implies "staged"
+    const int n = min(mc_r - (c0 + part2), 2);
+    if (n > 0) {
+      uint64_t* o = out + (int64_t)ho_r + c0 + part2;
+      if (n == 2 && base16 && (ho_r & 1) == 0) {
+        *reinterpret_cast<u64x2*>(o) = u64x2{v0, v1};  // dwordx4
+      } else {
+        o[0] = v0;
+        if (n == 2) o[1] = v1;
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// k_fnv_chain_tr's chunk body over wave g's own image, wave_k[g] trips.
+// One-wave workgroups, block g = wave g: the longest waves are dispatched
+// first.  Lane l is prompt perm[64 g + l]; -1 is a chain of no chunks.
+// out: CSR, chunk c of prompt p at out[h_off[p] + c]; nothing outside
+// [0, total_chunks) is written.
+template <int BS>
+__global__ void __launch_bounds__(64) k_fnv_chain_waves(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    uint64_t init, uint64_t* __restrict__ out) {
+  __shared__ uint64_t stage[64 * CHAIN_STAGE_ROW];
+  const int g = blockIdx.x;
+  const int wl = threadIdx.x;
+  const int p = perm[(int64_t)g * 64 + wl];
+  const int pc = max(p, 0);
+  const int mc = p >= 0 ? n_chunks[pc] : 0;
+  const int ho = h_off[pc];
+  const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
+  const int32_t* tokens_t = img + img_off[g] + wl;
+  uint64_t h = init;
+  for (int c = 0; c < K; ++c) {
+    uint32_t tok[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j)
+      tok[j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * 64];
+    const bool active = c < mc;
+    const bool wide = __all(!active || h > 0xFFFFFFFFull);
+    const uint64_t h2 = chunk_hash_fast(h, tok, BS, wide);
+    h = active ? h2 : h;
+    const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
+    stage[wl * CHAIN_STAGE_ROW + cc] = h;  // read back only where c < mc
+    if (cc == CHAIN_STAGE_CHUNKS - 1 || c == K - 1)
+      chain_flush_csr(stage, out, ho, mc, wl, c);
+  }
+}
+
+// k_sha_chain_tr over the per-wave images: wave_k[g] as the loop bound,
+// CSR stores of active chunks only, no zero-fill tail.  The waves of a
+// workgroup have different trip counts, which is safe: nothing in
+// chunk_hash_sha256_wave is a workgroup barrier (each lane packs into its
+// own LDS column, the votes are wave-wide), and neither is anything here.
+template <int BS, int ALGO>
+__global__ void k_sha_chain_waves(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int G, uint64_t init, uint64_t* __restrict__ out) {
+  constexpr int NT = sha_tr_threads(BS);
+  __shared__ uint32_t sha_words[sha_tr_words(BS) * NT];
+  const int wl = threadIdx.x & 63;
+  const int g = __builtin_amdgcn_readfirstlane(
+      (int)blockIdx.x * (NT / 64) + (int)(threadIdx.x >> 6));
+  if (g >= G) return;  // a whole wave, and no barrier follows
+  const int p = perm[(int64_t)g * 64 + wl];
+  const int pc = max(p, 0);
+  const int mc = p >= 0 ? n_chunks[pc] : 0;
+  uint64_t* o = out + h_off[pc];
+  const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
+  const int32_t* tokens_t = img + img_off[g] + wl;
+  ShaLdsCol<NT> col{sha_words + threadIdx.x};
+  uint64_t h = init;
+  for (int c = 0; c < K; ++c) {
+    const bool active = c < mc;
+    uint32_t tok[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j)
+      tok[j] = (uint32_t)tokens_t[(int64_t)(c * BS + j) * 64];
+    const uint64_t h2 = chunk_hash_sha256_wave(
+        h, tok, BS, sha_digest_word(ALGO), col, active, ShaWaveAny{});
+    h = active ? h2 : h;
+    if (active) o[c] = h;
+  }
+}
+
 template <int ALGO>
 __global__ void k_event_chains_ev(
     Table v, const int32_t* __restrict__ tokens_t,  // [maxT, E]
@@ -2169,48 +2360,6 @@ static void dispatch_chain_block_size(int64_t block_size, F&& f) {
       TORCH_CHECK(false, "hash_chain_tr supports block sizes 4/8/16/32/64; "
                          "use gpu_hash_chain for other sizes");
   }
-}
-
-// Host half of the ragged staging: what the offsets say about a batch.
-// One int32 buffer [n_chunks (B) | token offsets (B+1)] so that both go
-// up in one copy.
-struct RaggedPlan {
-  int64_t B = 0, max_k = 0, total_chunks = 0;
-  at::Tensor host;  // int32 [2B+1]
-};
-
-static RaggedPlan plan_ragged(const at::Tensor& tokens,
-                              const at::Tensor& offsets, int64_t block_size) {
-  TORCH_CHECK(block_size > 0, "block_size must be positive");
-  TORCH_CHECK(offsets.dtype() == at::kLong && offsets.dim() == 1 &&
-                  offsets.numel() >= 1,
-              "offsets must be an int64 [B+1] tensor");
-  TORCH_CHECK(tokens.dim() == 1 &&
-                  (tokens.dtype() == at::kLong || tokens.dtype() == at::kInt),
-              "tokens must be a flat int64 or int32 tensor");
-  auto off = offsets.to(at::kCPU).contiguous();
-  const int64_t* offp = off.data_ptr<int64_t>();
-  RaggedPlan p;
-  p.B = off.numel() - 1;
-  // the kernel trusts these: it reads tokens[off[b] + i] unchecked
-  TORCH_CHECK(offp[0] >= 0 && offp[p.B] <= tokens.numel(),
-              "offsets reach outside the token tensor");
-  TORCH_CHECK(offp[p.B] <= INT32_MAX,
-              "more than 2^31 - 1 tokens in one batch");
-  p.host = at::empty({2 * p.B + 1}, at::kInt);
-  int32_t* nc = p.host.data_ptr<int32_t>();
-  int32_t* o32 = nc + p.B;
-  for (int64_t b = 0; b < p.B; ++b) {
-    int64_t len = offp[b + 1] - offp[b];
-    TORCH_CHECK(len >= 0, "offsets must not decrease");
-    int64_t k = len / block_size;
-    nc[b] = (int32_t)k;
-    o32[b] = (int32_t)offp[b];
-    p.max_k = std::max(p.max_k, k);
-    p.total_chunks += k;
-  }
-  o32[p.B] = (int32_t)offp[p.B];
-  return p;
 }
 
 // -> {tokens_t int32 [max_k * block_size, B], n_chunks int32 [B]} on dev.
@@ -2758,6 +2907,123 @@ std::vector<at::Tensor> kvidx::gpu_topk_flat_tokens(
   return gpu_tiled_topk_rows(KVIDX_TABLE_ARGS, c.rows, c.n_keys, model_id,
                              filter_words, weights, num_pods, epoch, p.max_k,
                              n_tiers, top_n);
+}
+
+// The ragged device chain: plan (host) -> one upload -> k_stage_ragged_waves
+// -> k_*_chain_waves, on the current stream.  hashes int64 [total_chunks]
+// and h_off int32 [B+1] on `dev`; both undefined where the batch has no
+// whole chunk (nothing is uploaded or launched then).
+namespace kvidx {
+struct ChainedCsr {
+  WavePlan p;
+  at::Tensor hashes, h_off;
+};
+static ChainedCsr chain_ragged_waves(const at::Tensor& tokens_flat,
+                                     const at::Tensor& offsets,
+                                     int64_t init_hash_bits,
+                                     int64_t block_size, int64_t algo,
+                                     at::Device dev) {
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  // refused before anything is uploaded or launched
+  dispatch_chain_block_size(block_size, [](auto) {});
+  ChainedCsr c;
+  c.p = plan_ragged_waves(tokens_flat, offsets, block_size);
+  const WavePlan& p = c.p;
+  if (p.G == 0) return c;
+  const at::Tensor up = p.host.to(dev);
+  const at::Tensor img_off = p.img_off(up);
+  const int32_t* w = i32p(up);
+  const int32_t* n_chunks = w + p.at_n_chunks();
+  const int32_t* perm = w + p.at_perm();
+  const int32_t* wave_k = w + p.at_wave_k();
+  c.h_off = p.i32(up, p.at_h_off(), p.B + 1);
+  auto img = at::empty({p.image_elems}, up.options());
+  c.hashes = at::empty({p.total_chunks}, up.options().dtype(at::kLong));
+  auto tok = tokens_flat.is_cuda() ? tokens_flat.contiguous()
+                                   : tokens_flat.contiguous().to(dev);
+  const int G = (int)p.G;
+  auto stage = [&](auto* flat) {
+    using TokT = std::remove_const_t<std::remove_pointer_t<decltype(flat)>>;
+    hipLaunchKernelGGL(k_stage_ragged_waves<TokT>, dim3((unsigned)p.tiles),
+                       dim3(256), 0, STREAM, flat, w + p.at_tok_off(),
+                       n_chunks, perm, wave_k, img_off.data_ptr<int64_t>(),
+                       w + p.at_tile_start(), G, (int)block_size, i32p(img));
+  };
+  if (tok.dtype() == at::kLong)
+    stage(tok.data_ptr<int64_t>());
+  else
+    stage(tok.data_ptr<int32_t>());
+  dispatch_algo(algo, [&](auto A) {
+    dispatch_chain_block_size(block_size, [&](auto S) {
+      constexpr int AL = decltype(A)::value;
+      constexpr int BS = decltype(S)::value;
+      if constexpr (AL == ALGO_FNV64A) {
+        hipLaunchKernelGGL(k_fnv_chain_waves<BS>, dim3((unsigned)G), dim3(64),
+                           0, STREAM, i32p(img), img_off.data_ptr<int64_t>(),
+                           perm, wave_k, n_chunks, i32p(c.h_off),
+                           (uint64_t)init_hash_bits, u64p(c.hashes));
+      } else {
+        constexpr int NT = sha_tr_threads(BS);
+        auto kern = k_sha_chain_waves<BS, AL>;  // one macro argument
+        hipLaunchKernelGGL(kern,
+                           dim3((unsigned)((G + NT / 64 - 1) / (NT / 64))),
+                           dim3(NT), 0, STREAM, i32p(img),
+                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
+                           i32p(c.h_off), G, (uint64_t)init_hash_bits,
+                           u64p(c.hashes));
+      }
+    });
+  });
+  return c;
+}
+}  // namespace kvidx
+
+std::vector<at::Tensor> kvidx::gpu_hash_chain_ragged(at::Tensor tokens_flat,
+                                                     at::Tensor offsets,
+                                                     int64_t init_hash_bits,
+                                                     int64_t block_size,
+                                                     int64_t algo) {
+  at::Device dev = tokens_flat.is_cuda()
+                       ? tokens_flat.device()
+                       : at::Device(at::kCUDA, at::cuda::current_device());
+  auto c = chain_ragged_waves(tokens_flat, offsets, init_hash_bits, block_size,
+                              algo, dev);
+  if (c.p.G > 0) return {c.hashes, c.h_off};
+  auto opt = at::TensorOptions().device(dev);
+  return {at::empty({0}, opt.dtype(at::kLong)),
+          at::zeros({c.p.B + 1}, opt.dtype(at::kInt))};
+}
+
+at::Tensor kvidx::gpu_score_flat_tokens_ragged(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
+    int64_t block_size, int64_t n_tiers, int64_t algo) {
+  TORCH_CHECK(keys.is_cuda(), "table must live on the GPU");
+  auto c = chain_ragged_waves(tokens_flat, offsets, init_hash_bits, block_size,
+                              algo, keys.device());
+  if (c.p.G == 0)
+    return at::zeros({c.p.B, num_pods}, keys.options().dtype(at::kFloat));
+  return gpu_score_hashes(KVIDX_TABLE_ARGS, c.hashes, c.h_off, model_id,
+                          filter_words, weights, num_pods, epoch, c.p.max_k,
+                          n_tiers);
+}
+
+std::vector<at::Tensor> kvidx::gpu_topk_flat_tokens_ragged(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
+    int64_t block_size, int64_t n_tiers, int64_t algo, int64_t top_n) {
+  TORCH_CHECK(keys.is_cuda(), "table must live on the GPU");
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  auto c = chain_ragged_waves(tokens_flat, offsets, init_hash_bits, block_size,
+                              algo, keys.device());
+  if (c.p.G == 0)
+    return {at::full({c.p.B, top_n}, -1, keys.options().dtype(at::kInt)),
+            at::zeros({c.p.B, top_n}, keys.options().dtype(at::kFloat))};
+  return gpu_topk_hashes(KVIDX_TABLE_ARGS, c.hashes, c.h_off, model_id,
+                         filter_words, weights, num_pods, epoch, c.p.max_k,
+                         n_tiers, top_n);
 }
 
 void kvidx::gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,

@@ -7,6 +7,7 @@
 
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <vector>
 
@@ -33,6 +34,12 @@ std::vector<uint64_t> tokens_to_chunk_hashes_fast(std::vector<uint64_t> tokens,
 std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
                                          at::Tensor parents,
                                          int64_t block_size, int64_t algo);
+// The host plan of the ragged device chain (plan_ragged_waves below) as
+// CPU tensors: {perm int32 [64 G], wave_k int32 [G], img_off int64 [G+1],
+// tile_start int32 [G+1], h_off int32 [B+1]}.  In every build.
+std::vector<at::Tensor> plan_ragged_waves_op(at::Tensor tokens,
+                                             at::Tensor offsets,
+                                             int64_t block_size);
 
 // ---- table ops, CPU (cpu_ops.cpp) ------------------------------------
 void cpu_insert(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
@@ -215,6 +222,31 @@ std::vector<at::Tensor> gpu_topk_flat_tokens(
     int64_t model_id, at::Tensor filter_words, at::Tensor weights,
     int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
     int64_t block_size, int64_t n_tiers, int64_t algo, int64_t top_n);
+// The ragged device chain: flat tokens (host or device, int64 or int32) ->
+// {hashes int64 [total_chunks], h_off int32 [B+1]} on the device, the
+// layout and the content of hash_chain_batch with every parent
+// init_hash_bits.  Block sizes 4/8/16/32/64.  Stage and chain run over
+// per-wave images (plan_ragged_waves), so nothing is padded to the batch's
+// longest prompt and no image cap applies.
+std::vector<at::Tensor> gpu_hash_chain_ragged(at::Tensor tokens_flat,
+                                              at::Tensor offsets,
+                                              int64_t init_hash_bits,
+                                              int64_t block_size,
+                                              int64_t algo);
+// gpu_score_flat_tokens / gpu_topk_flat_tokens over the ragged chain:
+// stage -> chain -> gpu_score_hashes / gpu_topk_hashes on the CSR hashes,
+// on the current stream with no host wait in between.  Same results bit
+// for bit.
+at::Tensor gpu_score_flat_tokens_ragged(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
+    int64_t block_size, int64_t n_tiers, int64_t algo);
+std::vector<at::Tensor> gpu_topk_flat_tokens_ragged(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor offsets,
+    int64_t model_id, at::Tensor filter_words, at::Tensor weights,
+    int64_t num_pods, int64_t epoch, int64_t init_hash_bits,
+    int64_t block_size, int64_t n_tiers, int64_t algo, int64_t top_n);
 void gpu_apply_events(KVIDX_TABLE_PARAMS, at::Tensor tokens,
                       at::Tensor tok_off, at::Tensor ehashes,
                       at::Tensor eh_off, at::Tensor parents,
@@ -342,6 +374,132 @@ inline int64_t topk_rows_checked(const at::Tensor& scores, int64_t top_n) {
   TORCH_CHECK(P >= 1 && P <= MAX_PODS, "scores must have 1..", MAX_PODS,
               " pod columns");
   return P;
+}
+
+// Host half of the ragged staging: what the offsets say about a batch.
+// One int32 buffer [n_chunks (B) | token offsets (B+1)] so that both go
+// up in one copy.
+struct RaggedPlan {
+  int64_t B = 0, max_k = 0, total_chunks = 0;
+  at::Tensor host;  // int32 [2B+1]
+};
+
+inline RaggedPlan plan_ragged(const at::Tensor& tokens,
+                              const at::Tensor& offsets, int64_t block_size) {
+  TORCH_CHECK(block_size > 0, "block_size must be positive");
+  TORCH_CHECK(offsets.dtype() == at::kLong && offsets.dim() == 1 &&
+                  offsets.numel() >= 1,
+              "offsets must be an int64 [B+1] tensor");
+  TORCH_CHECK(tokens.dim() == 1 &&
+                  (tokens.dtype() == at::kLong || tokens.dtype() == at::kInt),
+              "tokens must be a flat int64 or int32 tensor");
+  auto off = offsets.to(at::kCPU).contiguous();
+  const int64_t* offp = off.data_ptr<int64_t>();
+  RaggedPlan p;
+  p.B = off.numel() - 1;
+  // the kernel trusts these: it reads tokens[off[b] + i] unchecked
+  TORCH_CHECK(offp[0] >= 0 && offp[p.B] <= tokens.numel(),
+              "offsets reach outside the token tensor");
+  TORCH_CHECK(offp[p.B] <= INT32_MAX,
+              "more than 2^31 - 1 tokens in one batch");
+  p.host = at::empty({2 * p.B + 1}, at::kInt);
+  int32_t* nc = p.host.data_ptr<int32_t>();
+  int32_t* o32 = nc + p.B;
+  for (int64_t b = 0; b < p.B; ++b) {
+    int64_t len = offp[b + 1] - offp[b];
+    TORCH_CHECK(len >= 0, "offsets must not decrease");
+    int64_t k = len / block_size;
+    nc[b] = (int32_t)k;
+    o32[b] = (int32_t)offp[b];
+    p.max_k = std::max(p.max_k, k);
+    p.total_chunks += k;
+  }
+  o32[p.B] = (int32_t)offp[p.B];
+  return p;
+}
+
+// Host half of the ragged (wave-tiled) device chain.  The prompts, sorted
+// by whole chunks descending (stable: ties by ascending prompt index), are
+// cut into waves of 64; wave g gets a token image int32 [wave_k[g] *
+// block_size][64] of its own, only as tall as its longest prompt, and the
+// hashes come out in CSR form in the caller's prompt order.  Waves made up
+// of zero-chunk prompts alone are not planned: G counts waves with
+// wave_k > 0.
+// One int32 buffer, so that everything goes up in one copy:
+//   [img_off int64 (G+1) | n_chunks (B) | tok_off (B+1) | h_off (B+1) |
+//    perm (64 G) | wave_k (G) | tile_start (G+1)]
+//  - perm[64 g + r]: the prompt in row r of wave g, -1 past the batch;
+//  - wave_k[g]: n_chunks of the wave's first prompt, its maximum;
+//  - img_off[g]: element offset of wave g's image, the sum of wave_k *
+//    block_size * 64 before it, so every image starts on a 256 B line;
+//    img_off[G] is the size of the whole image;
+//  - tile_start[g]: 64-position staging tiles before wave g;
+//  - h_off: exclusive prefix sum of n_chunks in the caller's order.
+// img_off leads the buffer, which keeps its int64 words 8-byte aligned.
+struct WavePlan {
+  int64_t B = 0, G = 0, max_k = 0, total_chunks = 0;
+  int64_t image_elems = 0, tiles = 0;
+  at::Tensor host;  // int32 [2 (G+1) + 3 B + 2 + 66 G + 1]
+  int64_t at_img_off() const { return 0; }
+  int64_t at_n_chunks() const { return 2 * (G + 1); }
+  int64_t at_tok_off() const { return at_n_chunks() + B; }
+  int64_t at_h_off() const { return at_tok_off() + B + 1; }
+  int64_t at_perm() const { return at_h_off() + B + 1; }
+  int64_t at_wave_k() const { return at_perm() + 64 * G; }
+  int64_t at_tile_start() const { return at_wave_k() + G; }
+  int64_t words() const { return at_tile_start() + G + 1; }
+  // pieces of `buf`, the host buffer or its copy on the device
+  at::Tensor i32(const at::Tensor& buf, int64_t at, int64_t n) const {
+    return buf.slice(0, at, at + n);
+  }
+  at::Tensor img_off(const at::Tensor& buf) const {
+    return buf.slice(0, 0, 2 * (G + 1)).view(at::kLong);
+  }
+};
+
+inline WavePlan plan_ragged_waves(const at::Tensor& tokens,
+                                  const at::Tensor& offsets,
+                                  int64_t block_size) {
+  const RaggedPlan r = plan_ragged(tokens, offsets, block_size);
+  const int32_t* nc = r.host.data_ptr<int32_t>();
+  WavePlan p;
+  p.B = r.B;
+  p.max_k = r.max_k;
+  p.total_chunks = r.total_chunks;
+  TORCH_CHECK(p.total_chunks <= INT32_MAX,
+              "more than 2^31 - 1 chunks in one batch");
+  std::vector<int32_t> order(p.B);
+  for (int64_t b = 0; b < p.B; ++b) order[b] = (int32_t)b;
+  std::stable_sort(order.begin(), order.end(),
+                   [nc](int32_t a, int32_t b) { return nc[a] > nc[b]; });
+  int64_t live = 0;  // prompts with a whole chunk: they sort first
+  while (live < p.B && nc[order[live]] > 0) ++live;
+  p.G = (live + 63) / 64;
+  p.host = at::empty({p.words()}, at::kInt);
+  int32_t* w = p.host.data_ptr<int32_t>();
+  int64_t* img_off = reinterpret_cast<int64_t*>(w);
+  std::copy(nc, nc + 2 * p.B + 1, w + p.at_n_chunks());  // and tok_off
+  int32_t* h_off = w + p.at_h_off();
+  h_off[0] = 0;
+  for (int64_t b = 0; b < p.B; ++b) h_off[b + 1] = h_off[b] + nc[b];
+  int32_t* perm = w + p.at_perm();
+  int32_t* wave_k = w + p.at_wave_k();
+  int32_t* tile_start = w + p.at_tile_start();
+  img_off[0] = 0;
+  tile_start[0] = 0;
+  for (int64_t g = 0; g < p.G; ++g) {
+    for (int64_t i = 64 * g; i < 64 * g + 64; ++i)
+      perm[i] = i < p.B ? order[i] : -1;
+    const int64_t rows = (int64_t)nc[order[64 * g]] * block_size;
+    wave_k[g] = nc[order[64 * g]];
+    img_off[g + 1] = img_off[g] + rows * 64;
+    const int64_t tiles = tile_start[g] + (rows + 63) / 64;
+    TORCH_CHECK(tiles <= INT32_MAX, "too many staging tiles in one batch");
+    tile_start[g + 1] = (int32_t)tiles;
+  }
+  p.image_elems = img_off[p.G];
+  p.tiles = tile_start[p.G];
+  return p;
 }
 
 // Runs f(std::integral_constant<int, ALGO>) for a native chain algo id

@@ -1069,7 +1069,15 @@ at::Tensor wire_score_flat(at::Tensor keys, at::Tensor meta, at::Tensor stamp,
   int64_t B = offsets.numel() - 1;
 #ifdef KVIDX_WITH_HIP
   // device_chain=1 (the caller's routing decision, indexer.py
-  // plan_read_route): raw tokens go up and the chain runs on the GPU too.
+  // plan_read_route): raw tokens go up and the chain runs on the GPU too;
+  // device_chain=2: over per-wave images and CSR hashes (the ragged ops).
+  if (device_chain == 2 && keys.is_cuda())
+    return gpu_score_flat_tokens_ragged(
+               keys, meta, stamp, pods, e_keys, e_meta, e_vals, pods_per_key,
+               tokens_flat, offsets, model_id, filter_words, weights,
+               num_pods, epoch, init_hash_bits, block_size, n_tiers, algo)
+        .to(at::kCPU, /*non_blocking=*/false)
+        .contiguous();
   if (device_chain && keys.is_cuda())
     return gpu_score_flat_tokens(keys, meta, stamp, pods, e_keys, e_meta,
                                  e_vals, pods_per_key, tokens_flat, offsets,

@@ -97,11 +97,14 @@ class WireIndexerService:
 
     def _device_chain(self, idx, offsets, bs) -> int:
         """The per-batch routing decision (indexer.plan_read_route) as
-        wire_score_flat's trailing argument."""
+        wire_score_flat's trailing argument: 0 CPU chain, 1 device chain
+        over the padded image, 2 over the ragged one."""
         tp = self.indexer.tokens_processor
         route = plan_read_route(offsets, bs, tp.config.hash_algo,
                                 idx.table.is_cuda, self.indexer.config)
-        return 1 if route.device else 0
+        if not route.device:
+            return 0
+        return 2 if route.ragged else 1
 
     @staticmethod
     def _run_flat(idx, *args):
