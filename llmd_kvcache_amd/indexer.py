@@ -376,8 +376,12 @@ class Indexer:
         bs = tp.block_size
         B = int(offsets.numel()) - 1
         init = _to_i64(tp.config.init_hash())
-        route = plan_read_route(offsets, bs, tp.config.hash_algo,
-                                idx.table.is_cuda, self.config)
+        # the device-chain route probes the local table only: not for an
+        # index whose read is a collective over hashes (ShardedIndex)
+        route = plan_read_route(
+            offsets, bs, tp.config.hash_algo,
+            idx.table.is_cuda and getattr(idx, "reads_are_local", True),
+            self.config)
         if route.device and route.max_k > 0:
             # raw tokens up, chain + probe + walk on the device: same
             # chain function, same walk, the same scores bit for bit
@@ -434,7 +438,8 @@ class Indexer:
         [(pod, score), ...], highest score first, pods that score 0 left
         out; works on every backend.
 
-        Table backends (fused_top_pods) pick on the table's device and
+        Table backends (fused_top_pods; a ShardedIndex or its service
+        picks from the merged masks) pick on the table's device and
         order equal scores by LOWEST POD ID.  Every other backend, and a
         table backend under a hash algorithm without a native chain, sorts
         the score_tokens_batch maps by (-score, pod name): equal scores

@@ -35,6 +35,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cpu_get_request_keys", &kvidx::cpu_get_request_keys);
   m.def("cpu_score_topk", &kvidx::cpu_score_topk, py::arg("scores"),
         py::arg("top_n"));
+  m.def("cpu_topk_from_masks", &kvidx::cpu_topk_from_masks, py::arg("masks"),
+        py::arg("offsets"), py::arg("weights"), py::arg("num_pods"),
+        py::arg("top_n"));
   m.attr("MAX_TOPK") = kvidx::MAX_TOPK;
 #ifdef KVIDX_WITH_HIP
   m.attr("HAS_HIP") = true;
@@ -78,6 +81,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_topk_rows", &kvidx::gpu_topk_rows, py::arg("scores"),
         py::arg("top_n"));
   m.def("gpu_topk_hashes", &kvidx::gpu_topk_hashes);
+  m.def("gpu_topk_from_masks", &kvidx::gpu_topk_from_masks, py::arg("masks"),
+        py::arg("offsets"), py::arg("weights"), py::arg("num_pods"),
+        py::arg("top_n"));
   // the fused ops for any prompt length and fleet: keys tiled through LDS
   m.def("tiled_score_tile_keys", &kvidx::tiled_score_tile_keys,
         py::arg("n_tiers"), py::arg("W"));

@@ -328,6 +328,8 @@ at::Tensor kvidx::cpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
         for (int64_t w = 0; w < W; ++w) {
           uint64_t cur = 0;
           for (int t = 0; t < T; ++t) cur |= mk[t * W + w];
+          // bits at or past num_pods have no column in out
+          if (w == W - 1 && (num_pods & 63)) cur &= (1ull << (num_pods & 63)) - 1;
           uint64_t act = (k == 0) ? cur : (active[w] & cur);
           active[w] = act;
           if (act) any = true;
@@ -378,6 +380,29 @@ std::vector<at::Tensor> kvidx::cpu_score_topk(at::Tensor scores,
     }
   });
   return {ids, out};
+}
+
+// The walk, then the pick: the contract of gpu_topk_from_masks, and what
+// the sharded read path runs on CPU tables.
+std::vector<at::Tensor> kvidx::cpu_topk_from_masks(at::Tensor masks,
+                                                   at::Tensor offsets,
+                                                   at::Tensor weights,
+                                                   int64_t num_pods,
+                                                   int64_t top_n) {
+  TORCH_CHECK(!masks.is_cuda() && masks.dtype() == at::kLong &&
+                  masks.dim() == 3,
+              "masks must be an int64 [Ktot, n_tiers, W] host tensor");
+  TORCH_CHECK(offsets.dtype() == at::kInt && offsets.numel() >= 1,
+              "offsets must be an int32 [B+1] tensor");
+  TORCH_CHECK(num_pods >= 1 && num_pods <= MAX_PODS, "num_pods must be 1..",
+              MAX_PODS);
+  TORCH_CHECK(masks.size(1) >= 1 && masks.size(1) <= MAX_TIERS &&
+                  weights.numel() >= masks.size(1),
+              "n_tiers must be 1..", MAX_TIERS, ", with a weight each");
+  TORCH_CHECK(masks.size(2) == pod_words(num_pods),
+              "masks must hold pod_words(num_pods) words per tier");
+  return cpu_score_topk(
+      cpu_score_from_masks(masks, offsets, weights, num_pods), top_n);
 }
 
 void kvidx::cpu_evict(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,

@@ -1350,6 +1350,198 @@ __global__ void __launch_bounds__(64) k_score_from_masks(
   }
 }
 
+// ---- merged masks -> top-n, one launch ----------------------------------
+// k_score_from_masks with tiled_score_body's work split and the pick
+// inside: one workgroup of 256 per prompt, wave v owns words v, v + 4, ...
+// (WPW of them at most, skipped wave-uniformly past W), lane l is pod bit
+// l, score[] / active[] in registers for the whole prompt.  The [B,
+// num_pods] matrix never exists.
+//
+// A prompt's masks are one contiguous span of K * T * W words.  It passes
+// through LDS in tiles of KT keys (tiled_score_tile_keys), two buffers
+// [KT, T, W], software-pipelined with ONE barrier per tile:
+//   issue tile i + 1's global loads into registers (thread t takes vectors
+//   t, t + 256, ..., NV at most) | walk tile i out of buffer i & 1 | write
+//   the registers to buffer (i + 1) & 1, which was last read before the
+//   previous barrier | barrier.
+// The loads are in flight for the length of the walk.  V16: 16-byte
+// vectors, chosen on the host where T * W is even and the base is 16-byte
+// aligned (every span then starts and ends on a 16-byte boundary); else
+// 8-byte vectors, twice as many.
+//
+// Early exit: a word whose active set emptied is never walked again.  A
+// wave that still holds a live word after tile i stores i + 1 into the
+// vote word before the barrier; a thread that then reads less than i + 1
+// knows that nobody can score any more and leaves - walk and loads end
+// together (one tile was loaded ahead).  The word only ever grows and live
+// words only ever die, so a wave already in step i + 1 can only have
+// written what keeps a slower thread in the loop, and nothing is reset.
+//
+// The walk takes a tile 64 keys at a time per word: one LDS read per tier
+// with a key in every lane, then 64 steps fed through readlane
+// (score_walk_lane).  A step per LDS round trip, which is what
+// score_walk_step over LDS costs, measured slower than k_score_from_masks'
+// scalar loads (profiles/r15_masks_topk.md).
+//
+// Scores are bit-identical to cpu_score_from_masks': score_walk_step's
+// arithmetic per pod in key order.  Epilogue: tiled_finish<WPW>(TopkOut), the exchange
+// area over buffer 0 behind the last barrier.
+// score_walk_step for key j of a chunk whose tier words sit one key per
+// lane in m[]: the same cur / wmax / score arithmetic in the same tier
+// order, the words taken from lane j (wave-uniform) instead of from memory.
+DEV int score_walk_lane(const unsigned long long (&m)[MAX_TIERS], int j,
+                        int n_tiers, const float (&wt)[MAX_TIERS], int lane,
+                        bool first, int& active, float& score) {
+  int cur = 0;
+  float wmax = 0.f;
+#pragma unroll
+  for (int t = 0; t < MAX_TIERS; ++t) {
+    if (t < n_tiers) {
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)m[t], j);
+      const uint32_t hi =
+          (uint32_t)__builtin_amdgcn_readlane((int)(m[t] >> 32), j);
+      if (((((uint64_t)hi << 32) | lo) >> lane) & 1) {
+        cur = 1;
+        wmax = fmaxf(wmax, wt[t]);
+      }
+    }
+  }
+  const int act = first ? cur : (active & cur);
+  active = act;
+  if (act) score += wmax;
+  return act;
+}
+
+template <bool V16>
+struct MaskVec {
+  using type = unsigned long long;
+  static constexpr int NV = 16, WORDS = 1;
+};
+// a native vector, not ulonglong2: the struct wrapper keeps stage[] out of
+// registers (the array went to scratch with it)
+typedef unsigned long long mask_u64x2 __attribute__((ext_vector_type(2)));
+template <>
+struct MaskVec<true> {
+  using type = mask_u64x2;
+  static constexpr int NV = 8, WORDS = 2;
+};
+// Host and device agree on what a thread can stage: NV vectors.
+template <bool V16>
+constexpr int mask_tile_max_words() {
+  return MaskVec<V16>::NV * MaskVec<V16>::WORDS * 256;
+}
+
+template <int WPW, bool V16>
+__global__ void __launch_bounds__(256) k_topk_from_masks(
+    const unsigned long long* __restrict__ masks,  // [Ktot, T, W]
+    const int32_t* __restrict__ offsets,           // [B+1]
+    int Ktot, const float* __restrict__ weights, int T, int num_pods, int W,
+    int KT, TopkOut out) {
+  using Vec = typename MaskVec<V16>::type;
+  constexpr int NV = MaskVec<V16>::NV;
+  // 2 x [KT, T, W], vote; aligned for the 16-byte tile stores
+  extern __shared__ __attribute__((aligned(16))) unsigned long long
+      lds_mask_tiles[];
+  unsigned long long* const lds_masks = lds_mask_tiles;
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int TW = T * W;
+  const int tile_words = KT * TW;
+  volatile int* vote = reinterpret_cast<int*>(lds_masks + 2 * tile_words);
+  // offsets the caller got wrong shorten the span; they never leave masks
+  const int k_lo = min(max(offsets[b], 0), Ktot);
+  const int K = max(min(offsets[b + 1], Ktot) - k_lo, 0);
+  const int n_tiles = (K + KT - 1) / KT;
+  const unsigned long long* span = masks + (size_t)k_lo * TW;
+
+  float score[WPW];
+  int active[WPW];
+  unsigned live = 0;  // bit j: word wave + 4 j can still score
+#pragma unroll
+  for (int j = 0; j < WPW; ++j) {
+    score[j] = 0.f;
+    active[j] = 0;
+    if (wave + 4 * j < W) live |= 1u << j;
+  }
+
+  float wt[MAX_TIERS];
+#pragma unroll
+  for (int t = 0; t < MAX_TIERS; ++t) wt[t] = t < T ? weights[t] : 0.f;
+
+  Vec stage[NV];
+  // vectors of tile i: whole, because a tile is whole keys of TW words
+  auto tile_vecs = [&](int i) {
+    return min(KT, K - i * KT) * TW / MaskVec<V16>::WORDS;
+  };
+  auto fetch = [&](int i) {  // global -> registers
+    const Vec* src =
+        reinterpret_cast<const Vec*>(span + (size_t)i * tile_words);
+    const int n = tile_vecs(i);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int x = j * 256 + (int)threadIdx.x;
+      if (x < n) stage[j] = src[x];
+    }
+  };
+  auto park = [&](int i) {  // registers -> buffer i & 1
+    Vec* dst = reinterpret_cast<Vec*>(lds_masks + (i & 1) * tile_words);
+    const int n = tile_vecs(i);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int x = j * 256 + (int)threadIdx.x;
+      if (x < n) dst[x] = stage[j];
+    }
+  };
+
+  if (threadIdx.x == 0) *vote = 0;
+  if (n_tiles > 0) {
+    fetch(0);
+    park(0);
+  }
+  __syncthreads();
+  for (int i = 0; i < n_tiles; ++i) {
+    const bool more = i + 1 < n_tiles;
+    if (more) fetch(i + 1);
+    const int k0 = i * KT;
+    const int len = min(KT, K - k0);
+    const unsigned long long* cbuf = lds_masks + (i & 1) * tile_words;
+#pragma unroll
+    for (int jw = 0; jw < WPW; ++jw) {
+      if (!((live >> jw) & 1)) continue;  // past W, or its set is empty
+      const unsigned long long* col = cbuf + wave + 4 * jw;
+      // 64 keys at a time: lane j reads key c0 + j's tier words, one LDS
+      // round trip for the chunk; step j then takes them from lane j
+      // through scalar registers, so no memory latency sits between two
+      // steps of the walk
+      for (int c0 = 0; c0 < len && ((live >> jw) & 1); c0 += 64) {
+        const int n = min(64, len - c0);
+        unsigned long long mine[MAX_TIERS];
+#pragma unroll
+        for (int t = 0; t < MAX_TIERS; ++t)
+          mine[t] = (t < T && lane < n)
+                        ? col[(size_t)(c0 + lane) * TW + t * W]
+                        : 0ull;
+        for (int j = 0; j < n; ++j) {
+          const int act = score_walk_lane(mine, j, T, wt, lane,
+                                          k0 + c0 + j == 0, active[jw],
+                                          score[jw]);
+          if (!__any(act)) {
+            live &= ~(1u << jw);
+            break;
+          }
+        }
+      }
+    }
+    if (live && lane == 0) *vote = i + 1;
+    if (more) park(i + 1);
+    __syncthreads();
+    if (*vote < i + 1) break;
+  }
+
+  tiled_finish<WPW>(out, b, score, W, num_pods, lds_masks);
+}
+
 // Batched hash chains: one LANE per prompt (chains are serial per prompt,
 // wave64-parallel across prompts; streaming CBOR->FNV keeps all state in
 // registers).  ALGO is the chain-function policy (kvidx_common.h
@@ -2697,6 +2889,63 @@ at::Tensor kvidx::gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
       i32p(offsets), weights.data_ptr<float>(), (int)T, (int)num_pods, (int)W,
       scores.data_ptr<float>());
   return scores;
+}
+
+// One k_topk_from_masks launch on the current stream, which has to be a
+// stream of the tensors' device.  The tile geometry is the tiled ops'
+// (tiled_geom_checked); the vector form is decided here, once per call.
+std::vector<at::Tensor> kvidx::gpu_topk_from_masks(at::Tensor masks,
+                                                   at::Tensor offsets,
+                                                   at::Tensor weights,
+                                                   int64_t num_pods,
+                                                   int64_t top_n) {
+  TORCH_CHECK(masks.is_cuda() && masks.dtype() == at::kLong &&
+                  masks.dim() == 3 && masks.is_contiguous(),
+              "masks must be a contiguous int64 [Ktot, n_tiers, W] device "
+              "tensor");
+  TORCH_CHECK(offsets.is_cuda() && offsets.dtype() == at::kInt &&
+                  offsets.dim() == 1 && offsets.numel() >= 1 &&
+                  offsets.is_contiguous(),
+              "offsets must be a contiguous int32 [B+1] device tensor");
+  const int64_t T = masks.size(1);
+  TORCH_CHECK(T >= 1 && T <= MAX_TIERS, "n_tiers must be 1..", MAX_TIERS);
+  TORCH_CHECK(weights.is_cuda() && weights.dtype() == at::kFloat &&
+                  weights.is_contiguous() && weights.numel() >= T,
+              "weights must be a contiguous float32 device tensor with one "
+              "entry per tier");
+  TORCH_CHECK(offsets.device() == masks.device() &&
+                  weights.device() == masks.device(),
+              "masks, offsets and weights must share one device");
+  TORCH_CHECK(masks.get_device() == at::cuda::current_device(),
+              "the current stream belongs to another device than masks");
+  TORCH_CHECK(top_n >= 1 && top_n <= MAX_TOPK, "top_n must be 1..", MAX_TOPK);
+  const TiledGeom g = tiled_geom_checked(num_pods, 0, T);
+  TORCH_CHECK(masks.size(2) == g.W, "masks must hold pod_words(num_pods) = ",
+              g.W, " words per tier");
+  const int64_t B = offsets.numel() - 1;
+  TORCH_CHECK(B <= INT32_MAX, "too many prompts in one batch");
+  auto r = topk_alloc(masks, B, top_n);
+  if (B == 0) return r;
+  const int64_t TW = T * g.W;
+  const bool v16 = TW % 2 == 0 &&
+                   reinterpret_cast<uintptr_t>(masks.data_ptr()) % 16 == 0;
+  // a thread stages one tile in NV registers
+  TORCH_CHECK(g.KT * TW <= (v16 ? mask_tile_max_words<true>()
+                                : mask_tile_max_words<false>()),
+              "mask tile out of range");
+  TORCH_CHECK(masks.size(0) <= INT32_MAX, "too many keys in one batch");
+  dispatch_tiled_wpw(g.W, [&](auto N) {
+    constexpr int WPW = decltype(N)::value;
+    auto kern = v16 ? k_topk_from_masks<WPW, true>
+                    : k_topk_from_masks<WPW, false>;
+    hipLaunchKernelGGL(
+        kern, dim3((unsigned)B), dim3(256), g.lds, STREAM,
+        reinterpret_cast<const unsigned long long*>(u64p(masks)),
+        (const int32_t*)i32p(offsets), (int)masks.size(0),
+        (const float*)weights.data_ptr<float>(), (int)T, (int)num_pods,
+        (int)g.W, (int)g.KT, topk_out(r, top_n));
+  });
+  return r;
 }
 
 at::Tensor kvidx::gpu_score_hashes(KVIDX_TABLE_PARAMS, at::Tensor hashes,

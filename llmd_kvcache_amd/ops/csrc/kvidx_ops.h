@@ -95,6 +95,15 @@ std::vector<at::Tensor> cpu_get_request_keys(KVIDX_TABLE_PARAMS,
 // serves top-n with (cpu_fused_score, then this), and the host statement
 // of the contract the GPU ops are tested against.
 std::vector<at::Tensor> cpu_score_topk(at::Tensor scores, int64_t top_n);
+// Top-n straight from (merged) masks: cpu_score_from_masks, then
+// cpu_score_topk.  masks int64 [Ktot, n_tiers, pod_words(num_pods)],
+// offsets int32 [B+1], weights float32 [n_tiers]; a prompt without keys
+// gives a row of (-1, 0.0f), and pod bits at or past num_pods never score.
+// The host statement of what gpu_topk_from_masks returns, bit for bit.
+std::vector<at::Tensor> cpu_topk_from_masks(at::Tensor masks,
+                                            at::Tensor offsets,
+                                            at::Tensor weights,
+                                            int64_t num_pods, int64_t top_n);
 
 #ifdef KVIDX_WITH_HIP
 // ---- table and chain ops, gfx950 (hip_ops.hip) -----------------------
@@ -134,6 +143,14 @@ at::Tensor gpu_fused_score_rows(KVIDX_TABLE_PARAMS, at::Tensor hashes,
                                 int64_t n_tiers);
 at::Tensor gpu_score_from_masks(at::Tensor masks, at::Tensor offsets,
                                 at::Tensor weights, int64_t num_pods);
+// The merged-mask walk with the pick inside (k_topk_from_masks): what
+// cpu_topk_from_masks takes, on one device, 1 <= num_pods <= MAX_PODS,
+// 1 <= top_n <= MAX_TOPK, 1 <= n_tiers <= MAX_TIERS.  One launch on the
+// current stream; the [B, num_pods] matrix never exists.
+std::vector<at::Tensor> gpu_topk_from_masks(at::Tensor masks,
+                                            at::Tensor offsets,
+                                            at::Tensor weights,
+                                            int64_t num_pods, int64_t top_n);
 // The one place that decides between the resident and the tiled fused
 // kernel: gpu_fused_score where its LDS holds the batch, else
 // gpu_tiled_score.  hashes int64 flat, offsets int32 [B+1], both on the

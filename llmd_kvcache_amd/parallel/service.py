@@ -14,6 +14,8 @@ collective, so raw payload bytes are shipped and decoded per rank.
 Protocol (collective ops driven by rank 0):
   ("events", [(pod, model, payload_bytes), ...])  apply on every rank
   ("score", hashes_i64_list, offsets, model, pods) score collectively
+  ("top", hashes_i64_list, offsets, model, pods, top_n, weights)
+                                                   score + top-n pick
   ("retire", pods)                                 purge + release ids
   ("clear", pods, model)                           purge, ids kept
   ("census", model)                                count, gather to rank 0
@@ -27,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import torch
 import torch.distributed as dist
 
-from ..kvblock.gpu_index import _to_i64
+from ..kvblock.gpu_index import _to_i64, check_top_n
 from ..kvblock.token_processor import ChunkedTokenDatabase
 from ..kvevents.events import decode_event_batch
 from .sharded import ShardedIndex, check_registry_sync, merge_census
@@ -82,6 +84,16 @@ class ShardedIndexService:
             h = torch.tensor(hashes, dtype=torch.int64)
             offs = torch.tensor(offsets, dtype=torch.int32)
             return self.sharded.sharded_scores(h, offs, model, set(pods))
+        if kind == "top":
+            # "score" with the pick where the merged masks are walked;
+            # staged as above, weights (floats or None) included
+            _, hashes, offsets, model, pods, top_n, weights = op
+            h = torch.tensor(hashes, dtype=torch.int64)
+            offs = torch.tensor(offsets, dtype=torch.int32)
+            w = None if weights is None else torch.tensor(
+                weights, dtype=torch.float32, device=self.sharded.device)
+            return self.sharded.sharded_top_pods(h, offs, model, set(pods),
+                                                 top_n, w)
         if kind == "retire":
             # Broadcast ops run in one total order on every rank, so the
             # ids come back at the same point of every rank's stream and
@@ -181,6 +193,32 @@ class ShardedIndexService:
             self._broadcast(op)
             scores = self._dispatch(op)
             return self.sharded.local.scores_to_map(scores)[0]
+
+    # The Indexer's table surface on rank 0: Indexer(kv_block_index=
+    # service).top_pods_flat_tokens / top_pods_tokens_batch (and so POST
+    # /score_batch with "top_k") broadcast a "top" op and pick on the
+    # device; the followers' serve() loops take part as for "score".
+    def fused_top_pods(self, hashes, counts_or_offsets, model_name,
+                       pod_identifier_set, weights=None, max_k=None,
+                       top_n: int = 1):
+        """ShardedIndex.fused_top_pods through the op order; the caller
+        holds registry.ids_shared() until top_to_lists, as there."""
+        assert self.rank == 0
+        offsets = counts_or_offsets.to(device="cpu", dtype=torch.int64)
+        if not self.sharded.table.is_cuda:  # counts
+            offsets = torch.cat([torch.zeros(1, dtype=torch.int64),
+                                 torch.cumsum(offsets, 0)])
+        op = ("top", hashes.tolist(), offsets.tolist(), model_name,
+              sorted(pod_identifier_set), check_top_n(top_n),
+              None if weights is None else weights.tolist())
+        self._broadcast(op)
+        return self._dispatch(op)
+
+    def __getattr__(self, name):
+        # registry, table, tier_weights, top_to_lists, ...: the shard's
+        if name == "sharded":
+            raise AttributeError(name)
+        return getattr(self.sharded, name)
 
     def retire_pods(self, pods: Sequence[str],
                     compact: bool = False) -> Dict[str, object]:

@@ -46,7 +46,8 @@ from typing import Dict, Optional, Sequence, Set, Tuple
 import torch
 import torch.distributed as dist
 
-from ..kvblock.gpu_index import TableIndex, TableIndexConfig, _to_i64
+from ..kvblock.gpu_index import (TableIndex, TableIndexConfig, _to_i64,
+                                 check_top_n, check_topk_weights)
 
 # payload threshold for switching all_reduce -> reduce_scatter+all_gather
 # (below this the extra collective's latency dominates its volume saving)
@@ -151,6 +152,35 @@ class ShardedIndex:
         reduce_scatter) depends only on symmetric quantities (K, B,
         world, backend, registry shape), so all ranks always pick the
         same collective sequence."""
+        return self._read(hashes, offsets, model_name, pod_identifier_set,
+                          weights, None)
+
+    def sharded_top_pods(
+        self,
+        hashes: torch.Tensor,
+        offsets: torch.Tensor,
+        model_name: str,
+        pod_identifier_set: Set[str],
+        top_n: int,
+        weights: Optional[torch.Tensor] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """sharded_scores with each prompt's best top_n pods (1..MAX_TOPK)
+        picked where the merged masks are walked: all ranks return the
+        same (ids int32 [B, top_n], scores float32 [B, top_n]) in the
+        rank_key order (score > 0 only, highest first, equal scores by
+        ascending pod id, (-1, 0.0) in unused slots) - cpu_score_topk of
+        what sharded_scores returns, without the [B, num_pods] matrix: on
+        a GPU table the walk and the pick are one kernel, and the
+        reduce_scatter strategy gathers 8 * top_n bytes per prompt in
+        place of 4 * num_pods.  Same collective-participation guarantee,
+        same error flag, same strategy choice as sharded_scores."""
+        return self._read(hashes, offsets, model_name, pod_identifier_set,
+                          weights, check_top_n(top_n))
+
+    def _read(self, hashes, offsets, model_name, pod_identifier_set,
+              weights, top_n):
+        """Probe, merge, walk: top_n None ends in the score matrix, a
+        number in the top-n pair."""
         K = int(hashes.numel())
         B = int(offsets.numel()) - 1
         n_tiers = max(1, len(self.local.registry.id_to_tier))
@@ -162,6 +192,8 @@ class ShardedIndex:
         try:
             if weights is None:
                 weights = self.local.tier_weights()  # device alloc: guarded
+            if top_n is not None:
+                check_topk_weights(weights)
             hashes = hashes.to(device=self.device)
             model_id = self.registry.model_id(model_name)
             filt = self.local._filter_tensor(pod_identifier_set, num_pods)
@@ -181,11 +213,11 @@ class ShardedIndex:
         if use_rs:
             scores = self._merge_reduce_scatter(
                 masks, offs_cpu, weights, num_pods, n_tiers, W, K, B,
-                local_err is not None)
+                local_err is not None, top_n)
         else:
             scores = self._merge_all_reduce(
                 masks, offs_cpu, weights, num_pods, n_tiers, W, K,
-                local_err is not None)
+                local_err is not None, top_n)
         if local_err is not None:
             raise local_err
         if scores is None:
@@ -196,9 +228,10 @@ class ShardedIndex:
         return scores
 
     def _merge_all_reduce(self, masks, offs_cpu, weights, num_pods,
-                          n_tiers, W, K, failed: bool):
+                          n_tiers, W, K, failed: bool, top_n=None):
         """One all_reduce of [K*T*W + 1] (the +1 is the error flag).
-        Returns [B, num_pods] scores, or None if any rank flagged."""
+        Returns [B, num_pods] scores (top_n None) or the top-n pair, or
+        None if any rank flagged."""
         dev = self.local.table.keys.device
         buf = torch.zeros(K * n_tiers * W + 1, dtype=torch.int64, device=dev)
         if failed:
@@ -211,16 +244,20 @@ class ShardedIndex:
         if int(buf[-1].item()) != 0:
             return None
         merged = buf[: K * n_tiers * W].view(K, n_tiers, W)
+        if top_n is not None:
+            return self._walk_topk(merged, offs_cpu, weights, num_pods, top_n)
         return self._walk(merged, offs_cpu, weights, num_pods)
 
     def _merge_reduce_scatter(self, masks, offs_cpu, weights, num_pods,
-                              n_tiers, W, K, B, failed: bool):
+                              n_tiers, W, K, B, failed: bool, top_n=None):
         """Large-batch merge: prompts partitioned into world_size
         contiguous groups (balanced by key count); reduce_scatter hands
         each rank the merged masks for ITS group only ((N-1)/N of the
         mask volume moved once, vs twice for all_reduce); each rank walks
         its group (parallelizing the walk) and an all_gather of the small
-        [B_r, P] score rows rebuilds the full result on every rank."""
+        [B_r, P] score rows rebuilds the full result on every rank.  With
+        top_n the gathered rows are [B_r, 2 * top_n] int32 instead: the
+        ids, then the scores' bit patterns."""
         dev = self.local.table.keys.device
         TW = n_tiers * W
         bounds = _partition_prompts(offs_cpu, self.world_size)
@@ -253,12 +290,16 @@ class ShardedIndex:
             dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
             out.copy_(buf.view(self.world_size, seg)[self.rank])
 
-        # score rows for this rank's prompt group (+1 flag row)
-        P = num_pods
-        my = torch.zeros(bmax + 1, P, dtype=torch.float32, device=dev)
+        # result rows for this rank's prompt group (+1 flag row)
+        if top_n is None:
+            my = torch.zeros(bmax + 1, num_pods, dtype=torch.float32,
+                             device=dev)
+        else:
+            my = torch.zeros(bmax + 1, 2 * top_n, dtype=torch.int32,
+                             device=dev)
         peer_failed = int(out[-1].item()) != 0
         if failed or peer_failed:
-            my[bmax, 0] = 1.0
+            my[bmax, 0] = 1
         else:
             r = self.rank
             b_lo, b_hi = bounds[r], bounds[r + 1]
@@ -270,20 +311,30 @@ class ShardedIndex:
                         k_hi - k_lo, n_tiers, W)
                     local_offs = (offs_cpu[b_lo: b_hi + 1] - k_lo).to(
                         torch.int32)
-                    my[: b_hi - b_lo].copy_(
-                        self._walk(merged, local_offs, weights, num_pods))
+                    if top_n is None:
+                        my[: b_hi - b_lo].copy_(self._walk(
+                            merged, local_offs, weights, num_pods))
+                    else:
+                        ids, top = self._walk_topk(
+                            merged, local_offs, weights, num_pods, top_n)
+                        my[: b_hi - b_lo, :top_n].copy_(ids)
+                        my[: b_hi - b_lo, top_n:].copy_(
+                            top.view(torch.int32))
             except BaseException:
                 my.zero_()
-                my[bmax, 0] = 1.0
+                my[bmax, 0] = 1
         gathered = [torch.empty_like(my) for _ in range(self.world_size)]
         dist.all_gather(gathered, my, group=self.group)
-        if any(float(g[bmax, 0].item()) != 0.0 for g in gathered):
+        if any(g[bmax, 0].item() != 0 for g in gathered):
             return None
-        rows = [
+        rows = torch.cat([
             gathered[r][: bounds[r + 1] - bounds[r]]
             for r in range(self.world_size)
-        ]
-        return torch.cat(rows, dim=0)
+        ], dim=0)
+        if top_n is None:
+            return rows
+        return (rows[:, :top_n].contiguous(),
+                rows[:, top_n:].contiguous().view(torch.float32))
 
     def _walk(self, masks, offs_cpu, weights, num_pods):
         """Longest-prefix walk over merged masks -> [B, num_pods]."""
@@ -293,6 +344,56 @@ class ShardedIndex:
                 num_pods)
         return self.local.table.ops.cpu_score_from_masks(
             masks.contiguous(), offs_cpu, weights.cpu(), num_pods)
+
+    def _walk_topk(self, masks, offs_cpu, weights, num_pods, top_n):
+        """_walk with the pick inside -> (ids, scores) [B, top_n]: one
+        k_topk_from_masks launch on a GPU table, cpu_topk_from_masks on a
+        CPU one."""
+        ops = self.local.table.ops
+        if self.local.table.is_cuda:
+            ids, top = ops.gpu_topk_from_masks(
+                masks.contiguous(), offs_cpu.to(self.device), weights,
+                num_pods, top_n)
+        else:
+            ids, top = ops.cpu_topk_from_masks(
+                masks.contiguous(), offs_cpu, weights.cpu(), num_pods, top_n)
+        return ids, top
+
+    # -- the Indexer's table surface (TableIndex's signatures) -----------
+    # Every rank calls these with the same arguments, like every other
+    # read here.  reads_are_local tells the Indexer that a read is a
+    # collective over hashes: its device-chain route, which probes the
+    # local table only, is not for this index.
+    reads_are_local = False
+
+    @property
+    def table(self):
+        return self.local.table
+
+    def tier_weights(self, weight_map=None) -> torch.Tensor:
+        return self.local.tier_weights(weight_map)
+
+    def _num_pods_padded(self) -> int:
+        return self.local._num_pods_padded()
+
+    def fused_top_pods(self, hashes, counts_or_offsets, model_name,
+                       pod_identifier_set, weights=None, max_k=None,
+                       top_n: int = 1):
+        """TableIndex.fused_top_pods over the whole sharded table: counts
+        [B] on a CPU table, offsets [B+1] on a GPU one; max_k is not
+        needed.  The ids are registry pod ids, replicated on every rank:
+        hold registry.ids_shared() until top_to_lists has made names of
+        them."""
+        offsets = counts_or_offsets.to(device="cpu", dtype=torch.int32)
+        if not self.local.table.is_cuda:  # counts
+            offsets = torch.cat([
+                torch.zeros(1, dtype=torch.int32),
+                torch.cumsum(offsets, 0, dtype=torch.int32)])
+        return self.sharded_top_pods(hashes, offsets, model_name,
+                                     pod_identifier_set, top_n, weights)
+
+    def top_to_lists(self, ids, scores):
+        return self.local.top_to_lists(ids, scores)
 
     def score_keys(
         self, request_keys: Sequence, pod_identifier_set: Set[str]
