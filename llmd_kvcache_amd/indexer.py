@@ -69,11 +69,20 @@ class Config:
     # CSR hashes) instead of the CPU chain; "ragged" sends every batch of
     # the device route through them, and the cap does not apply
     device_chain_layout: str = "padded"
+    # block sizes of the device route: "fixed" is the five sizes the
+    # templated chain kernels are built for (DEVICE_CHAIN_BLOCK_SIZES),
+    # every other size chains on the CPU; "any" sends the other sizes
+    # 1..65535 through the ragged ops as well, whose stream chain kernels
+    # take the block size at run time, whatever device_chain_layout says
+    # (the padded ops refuse them) and without the image cap
+    device_chain_block_sizes: str = "fixed"
 
 
 _log = get_logger("indexer")
 
 DEVICE_CHAIN_BLOCK_SIZES = (4, 8, 16, 32, 64)
+# the stream chain kernels: a tokens-array header of at most three bytes
+STREAM_CHAIN_MAX_BLOCK_SIZE = 65535
 
 
 @dataclass
@@ -93,7 +102,12 @@ def plan_read_route(offsets, block_size: int, hash_algo: str,
     the transposed chain kernel has, image under the cap) and wanted
     ("on", or "auto" at or above the threshold); everything else takes
     the CPU chain.  Config.device_chain_layout decides whether the device
-    route is the padded or the ragged one; the ragged one has no cap."""
+    route is the padded or the ragged one; the ragged one has no cap.
+    Under Config.device_chain_block_sizes "any", a block size outside
+    DEVICE_CHAIN_BLOCK_SIZES takes the ragged device route too.  The
+    "auto" threshold was measured at block size 16 and chain cost goes by
+    the token, so for those sizes it is scaled (derived, not measured):
+    sum(n_chunks) * block_size >= device_chain_min_chunks * 16."""
     off = offsets.tolist() if hasattr(offsets, "tolist") else list(offsets)
     n_chunks = [(int(off[i + 1]) - int(off[i])) // block_size
                 for i in range(len(off) - 1)]
@@ -105,13 +119,20 @@ def plan_read_route(offsets, block_size: int, hash_algo: str,
         return route
     within_cap = image_bytes <= config.device_chain_max_image_bytes
     layout = config.device_chain_layout
-    ragged = layout == "ragged" or (layout == "over_cap" and not within_cap)
+    stream = (config.device_chain_block_sizes == "any"
+              and block_size not in DEVICE_CHAIN_BLOCK_SIZES
+              and 1 <= block_size <= STREAM_CHAIN_MAX_BLOCK_SIZE)
+    ragged = (stream or layout == "ragged"
+              or (layout == "over_cap" and not within_cap))
     if not (table_on_gpu and hash_algo in hashing.NATIVE_ALGO_IDS
-            and block_size in DEVICE_CHAIN_BLOCK_SIZES
+            and (stream or block_size in DEVICE_CHAIN_BLOCK_SIZES)
             and (within_cap or ragged)):
         return route
-    if mode == "auto" and sum(n_chunks) < config.device_chain_min_chunks:
-        return route
+    if mode == "auto":
+        floor = config.device_chain_min_chunks
+        if (sum(n_chunks) * block_size < floor * 16 if stream
+                else sum(n_chunks) < floor):
+            return route
     route.device = True
     route.ragged = ragged
     return route

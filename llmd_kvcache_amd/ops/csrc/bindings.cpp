@@ -21,6 +21,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tokens_to_chunk_hashes_fast", &kvidx::tokens_to_chunk_hashes_fast,
         py::arg("tokens"), py::arg("parent"), py::arg("block_size"),
         py::arg("algo") = 0);
+  m.def("tokens_to_chunk_hashes_stream", &kvidx::tokens_to_chunk_hashes_stream,
+        py::arg("tokens"), py::arg("parent"), py::arg("block_size"),
+        py::arg("algo") = 0);
   m.def("plan_ragged_waves", &kvidx::plan_ragged_waves_op, py::arg("tokens"),
         py::arg("offsets"), py::arg("block_size"));
   m.def("cpu_insert", &kvidx::cpu_insert);

@@ -186,6 +186,46 @@ std::vector<uint64_t> kvidx::tokens_to_chunk_hashes_fast(
   return out;
 }
 
+// Host twin of the stream chain kernels (any block size): the begin /
+// group / end pieces as k_fnv_chain_stream strings them together for algo
+// 0, chunk_hash_sha256_seg at the kernels' segment size over a plain word
+// column for the SHA algos.
+std::vector<uint64_t> kvidx::tokens_to_chunk_hashes_stream(
+    std::vector<uint64_t> tokens, uint64_t parent, int64_t block_size,
+    int64_t algo) {
+  TORCH_CHECK(stream_chain_block_size_ok(block_size),
+              "block_size must be in [1, 65535]");
+  std::vector<uint32_t> toks(tokens.begin(), tokens.end());
+  const int bs = (int)block_size;
+  int64_t n_chunks = (int64_t)toks.size() / bs;
+  std::vector<uint64_t> out;
+  out.reserve(n_chunks);
+  uint64_t h = parent;
+  const ChainShape shape = chain_shape(bs);
+  std::vector<uint32_t> words(sha_seg_words(SHA_SEG_TOKENS));
+  dispatch_algo(algo, [&](auto A) {
+    for (int64_t c = 0; c < n_chunks; ++c) {
+      const uint32_t* t = toks.data() + c * bs;
+      if constexpr (decltype(A)::value == ALGO_FNV64A) {
+        h = chunk_hash_begin(h, h > 0xFFFFFFFFull, shape);
+        for (int g = 0; g < shape.groups; ++g, t += CHAIN_GROUP)
+          h = chunk_hash_group(h, t);
+        h = chunk_hash_end(chunk_hash_group(h, t, shape.tail));
+      } else {
+        ShaHostBuf buf{words.data()};
+        auto load = [t](int first, int cnt, uint32_t* tok) {
+          std::copy(t + first, t + first + cnt, tok);
+        };
+        h = chunk_hash_sha256_seg<SHA_SEG_TOKENS>(
+            h, bs, load, sha_digest_word(decltype(A)::value), buf, true,
+            ShaHostAny{});
+      }
+      out.push_back(h);
+    }
+  });
+  return out;
+}
+
 // Batched chain hashing: tokens (int64 [total]), offsets (int64 [B+1]),
 // parents (int64 [B], u64 bits) -> per-prompt chunk hashes, flat, with
 // chunk-count offsets returned alongside.

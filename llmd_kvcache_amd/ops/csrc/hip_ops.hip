@@ -2222,6 +2222,115 @@ __global__ void k_sha_chain_waves(
   }
 }
 
+// ---------------------------------------------------------------------
+// The stream chain kernels: the ragged chain for ANY block size 1..65535.
+// The templated kernels above hold a chunk's tokens in tok[BS], so their
+// registers (FNV) and LDS columns (SHA) grow with the block size and stop
+// at 64.  These take block_size at run time and pass the tokens through a
+// fixed window: same work split (lane = prompt perm[64 g + l], wave_k[g]
+// trips over wave g's own image), same CSR output, footprint independent
+// of the block size.  block_size is a kernel argument, uniform over the
+// grid: everything derived from it is scalar, every branch on it a scalar
+// branch.
+// ---------------------------------------------------------------------
+
+// FNV-64a.  A chunk is chunk_hash_begin, block_size / 16 trips of a rolled
+// loop over groups of CHAIN_GROUP positions - 16 unconditional loads of one
+// 256 B line each into a statically indexed tok[16], then 16 unrolled
+// steps - one group of block_size % 16, chunk_hash_end.  The image is
+// position-major, so the walk over a wave's rows is one running pointer
+// from the first chunk to the last.
+__global__ void __launch_bounds__(64) k_fnv_chain_stream(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    uint64_t init, int block_size, uint64_t* __restrict__ out) {
+  __shared__ uint64_t stage[64 * CHAIN_STAGE_ROW];
+  const int g = blockIdx.x;
+  const int wl = threadIdx.x;
+  const int p = perm[(int64_t)g * 64 + wl];
+  const int pc = max(p, 0);
+  const int mc = p >= 0 ? n_chunks[pc] : 0;
+  const int ho = h_off[pc];
+  const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
+  const ChainShape s = chain_shape(block_size);
+  const int32_t* t = img + img_off[g] + wl;  // rows [0, K * block_size)
+  uint64_t h = init;
+  for (int c = 0; c < K; ++c) {
+    const bool active = c < mc;
+    const bool wide = __all(!active || h > 0xFFFFFFFFull);
+    uint64_t h2 = chunk_hash_begin(h, wide, s);
+#pragma unroll 1
+    for (int gi = 0; gi < s.groups; ++gi, t += CHAIN_GROUP * 64) {
+      uint32_t tok[CHAIN_GROUP];
+#pragma unroll
+      for (int j = 0; j < CHAIN_GROUP; ++j) tok[j] = (uint32_t)t[j * 64];
+      h2 = chunk_hash_group(h2, tok);
+    }
+    if (s.tail) {
+      uint32_t tok[CHAIN_GROUP];
+#pragma unroll
+      for (int j = 0; j < CHAIN_GROUP; ++j)  // rows past the chunk: not read
+        tok[j] = j < s.tail ? (uint32_t)t[j * 64] : 0u;
+      t += s.tail * 64;
+      h2 = chunk_hash_group(h2, tok, s.tail);
+    }
+    h2 = chunk_hash_end(h2);
+    h = active ? h2 : h;
+    const int cc = c & (CHAIN_STAGE_CHUNKS - 1);
+    stage[wl * CHAIN_STAGE_ROW + cc] = h;  // read back only where c < mc
+    if (cc == CHAIN_STAGE_CHUNKS - 1 || c == K - 1)
+      chain_flush_csr(stage, out, ho, mc, wl, c);
+  }
+}
+
+// SHA-256 over the same payload: chunk_hash_sha256_seg, SHA_SEG_TOKENS
+// tokens at a time through a column of sha_seg_words() words per lane
+// (28 KB for the wave, whatever the block size).  A segment's tokens are
+// loaded in one go - unconditionally for a whole segment, under scalar
+// branches for the last one - so one memory latency is paid per segment,
+// under which sit up to five compressions.  One-wave workgroups as the FNV
+// kernel: there is no workgroup barrier here or in the driver, and a wave
+// with fewer trips holds no other wave's LDS.
+template <int ALGO>
+__global__ void __launch_bounds__(64) k_sha_chain_stream(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    uint64_t init, int block_size, uint64_t* __restrict__ out) {
+  constexpr int SEG = SHA_SEG_TOKENS;
+  __shared__ uint32_t sha_words[sha_seg_words(SEG) * 64];
+  const int g = blockIdx.x;
+  const int wl = threadIdx.x;
+  const int p = perm[(int64_t)g * 64 + wl];
+  const int pc = max(p, 0);
+  const int mc = p >= 0 ? n_chunks[pc] : 0;
+  uint64_t* o = out + h_off[pc];
+  const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
+  const int32_t* chunk = img + img_off[g] + wl;  // rows [0, K * block_size)
+  ShaLdsCol<64> col{sha_words + wl};
+  uint64_t h = init;
+  for (int c = 0; c < K; ++c, chunk += (int64_t)block_size * 64) {
+    const bool active = c < mc;
+    auto load = [chunk](int first, int cnt, uint32_t (&tok)[SEG])
+                    __attribute__((always_inline)) {
+      const int32_t* t = chunk + (int64_t)first * 64;
+      if (cnt == SEG) {
+#pragma unroll
+        for (int j = 0; j < SEG; ++j) tok[j] = (uint32_t)t[j * 64];
+      } else {
+#pragma unroll
+        for (int j = 0; j < SEG; ++j)  // rows past the chunk: not read
+          tok[j] = j < cnt ? (uint32_t)t[j * 64] : 0u;
+      }
+    };
+    const uint64_t h2 = chunk_hash_sha256_seg<SEG>(
+        h, block_size, load, sha_digest_word(ALGO), col, active, ShaWaveAny{});
+    h = active ? h2 : h;
+    if (active) o[c] = h;
+  }
+}
+
 template <int ALGO>
 __global__ void k_event_chains_ev(
     Table v, const int32_t* __restrict__ tokens_t,  // [maxT, E]
@@ -2536,6 +2645,12 @@ static void check_padded_rows(const at::Tensor& hashes,
   TORCH_CHECK(n_keys.numel() == hashes.size(0),
               "n_keys must have one entry per row");
   TORCH_CHECK(max_k <= hashes.size(1), "max_k exceeds the row length");
+}
+
+// The block sizes the templated chain kernels are built for.
+static bool chain_block_size_templated(int64_t block_size) {
+  return block_size == 4 || block_size == 8 || block_size == 16 ||
+         block_size == 32 || block_size == 64;
 }
 
 // Runs f(std::integral_constant<int, BS>) for a block size the transposed
@@ -3173,8 +3288,12 @@ static ChainedCsr chain_ragged_waves(const at::Tensor& tokens_flat,
                                      int64_t block_size, int64_t algo,
                                      at::Device dev) {
   TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
-  // refused before anything is uploaded or launched
-  dispatch_chain_block_size(block_size, [](auto) {});
+  // the five block sizes of the templated kernels keep them; every other
+  // one the stream kernels take goes to those.  Refused before anything
+  // is uploaded or launched.
+  const bool templated = chain_block_size_templated(block_size);
+  TORCH_CHECK(templated || stream_chain_block_size_ok(block_size),
+              "the ragged device chain takes block sizes 1..65535");
   ChainedCsr c;
   c.p = plan_ragged_waves(tokens_flat, offsets, block_size);
   const WavePlan& p = c.p;
@@ -3202,6 +3321,24 @@ static ChainedCsr chain_ragged_waves(const at::Tensor& tokens_flat,
     stage(tok.data_ptr<int64_t>());
   else
     stage(tok.data_ptr<int32_t>());
+  if (!templated) {
+    // one-wave workgroups, block g = wave g, for either hash
+    dispatch_algo(algo, [&](auto A) {
+      constexpr int AL = decltype(A)::value;
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64), 0, STREAM,
+                           i32p(img), img_off.data_ptr<int64_t>(), perm,
+                           wave_k, n_chunks, i32p(c.h_off),
+                           (uint64_t)init_hash_bits, (int)block_size,
+                           u64p(c.hashes));
+      };
+      if constexpr (AL == ALGO_FNV64A)
+        launch(k_fnv_chain_stream);
+      else
+        launch(k_sha_chain_stream<AL>);
+    });
+    return c;
+  }
   dispatch_algo(algo, [&](auto A) {
     dispatch_chain_block_size(block_size, [&](auto S) {
       constexpr int AL = decltype(A)::value;

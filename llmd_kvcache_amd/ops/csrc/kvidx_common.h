@@ -224,6 +224,65 @@ KVIDX_HD uint64_t chunk_hash_fast(uint64_t parent, const TokT* tokens,
   return h;
 }
 
+// chunk_hash_fast in three pieces, for a chunk length known only at run
+// time (k_fnv_chain_stream and its host twin): begin feeds 0x83, the parent
+// and the tokens-array header, group feeds up to CHAIN_GROUP tokens from a
+// statically indexed array, end feeds the null.  A chunk is begin, n /
+// CHAIN_GROUP whole groups, one group of n % CHAIN_GROUP, end - the caller
+// rolls the group loop, so nothing here grows with n.
+// ChainShape holds what depends on n alone.  On the device n is uniform
+// over the grid: the shape is worked out once per kernel, lives in scalar
+// registers, and every branch on it below is a scalar branch.
+static constexpr int CHAIN_GROUP = 16;
+
+struct ChainShape {
+  uint32_t hdr;  // array(n) header, big-endian in the low hdr_len bytes
+  int hdr_len;   // 1, 2 or 3
+  int groups;    // whole groups per chunk
+  int tail;      // tokens of the last, partial group
+};
+// 1 <= n <= 0xFFFF (the ops check it)
+KVIDX_HD ChainShape chain_shape(int n) {
+  const uint32_t u = (uint32_t)n;
+  ChainShape s;
+  s.hdr_len = u < 24 ? 1 : u <= 0xFF ? 2 : 3;
+  s.hdr = u < 24 ? (0x80u | u) : u <= 0xFF ? (0x9800u | u) : (0x990000u | u);
+  s.groups = n / CHAIN_GROUP;
+  s.tail = n % CHAIN_GROUP;
+  return s;
+}
+
+// wide_parent as for chunk_hash_fast.
+KVIDX_HD uint64_t chunk_hash_begin(uint64_t parent, bool wide_parent,
+                                   const ChainShape& s) {
+  uint64_t h = fnv1a_64_byte(FNV64_OFFSET, 0x83);
+  if (wide_parent)
+    h = fnv_cbor_u64_wide(h, parent);
+  else
+    h = fnv_cbor_u64_branchless(h, parent, 0);
+  if (s.hdr_len > 2) h = fnv1a_64_byte(h, (uint8_t)(s.hdr >> 16));
+  if (s.hdr_len > 1) h = fnv1a_64_byte(h, (uint8_t)(s.hdr >> 8));
+  return fnv1a_64_byte(h, (uint8_t)s.hdr);
+}
+
+// tok[0..n), n <= CHAIN_GROUP.  Force-unrolled, so tok is only ever
+// indexed by constants; a whole group (the default n) has no branch left,
+// the tail group skips the steps it does not have by scalar branches (not
+// a break: a loop with an early exit stays rolled and indexes tok[] by a
+// register).
+template <typename TokT>
+KVIDX_HD uint64_t chunk_hash_group(uint64_t h, const TokT* tok,
+                                   int n = CHAIN_GROUP) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < CHAIN_GROUP; ++i)
+    if (i < n) h = fnv_cbor_u32_branchless(h, (uint32_t)tok[i], 0);
+  return h;
+}
+
+KVIDX_HD uint64_t chunk_hash_end(uint64_t h) { return fnv1a_64_byte(h, 0xF6); }
+
 // One chain link: FNV-64a(CBOR([parent, tokens[0..n), null])), streamed.
 template <typename TokT>
 KVIDX_HD uint64_t chunk_hash(uint64_t parent, const TokT* tokens, int n) {
@@ -527,6 +586,144 @@ struct ShaHostBuf {
 struct ShaHostAny {
   KVIDX_HD bool operator()(bool b) const { return b; }
 };
+
+// Segmented wave-convergent chain link, for a chunk length known only at
+// run time (k_sha_chain_stream and its host twin).  The whole-payload
+// driver above needs a column as long as the padded payload - 21 blocks at
+// n = 256 - so this one packs the payload SEG tokens at a time: after each
+// segment the wave compresses the whole blocks the segment completed (the
+// wave-maximum count, a per-lane select dropping the ones a lane does not
+// have, so the rounds never diverge), and each lane moves its incomplete
+// block to the front of its column.  The packer and st[8] stay in
+// registers across segments.  The last segment - the n % SEG tokens left,
+// possibly none - also takes null, the 0x80 byte, the zero fill and the
+// bit length.  One loop, one compression site.
+//
+// buf: sha_seg_words(SEG) words private to this lane.  The most a column
+// ever holds is a carried block short of one byte (15 words and 3 bytes
+// pending in the packer), SEG tokens of 5 bytes, null, 0x80 and the
+// 8 length bytes, rounded up to whole blocks.
+// load(first, cnt, tok): tokens [first, first + cnt) of the chunk into
+// tok[0..cnt), cnt <= SEG; n, and so cnt, is uniform over a wave.
+// active / any: as for chunk_hash_sha256_wave.
+static constexpr int SHA_SEG_TOKENS = 64;
+KVIDX_HD constexpr int sha_seg_words(int seg) {
+  return 16 * sha_blocks_for(63 + 5 * seg + 1);
+}
+
+// One item into the column at word widx: both words stored, widx moved on
+// by the whole ones (ShaPacker).
+template <class Buf>
+KVIDX_HD void sha_seg_put(ShaPacker& p, Buf& buf, int& widx, uint64_t item,
+                          int len) {
+  const int adv = p.put(item, len);
+  buf.st(widx, p.hi);
+  buf.st(widx + 1, p.lo);
+  widx += adv;
+}
+
+template <int SEG, class LoadFn, class Buf, class AnyFn>
+KVIDX_HD uint64_t chunk_hash_sha256_seg(uint64_t parent, int n, LoadFn load,
+                                        int digest_word, Buf& buf, bool active,
+                                        AnyFn any) {
+  constexpr int max_blocks = sha_seg_words(SEG) / 16;
+  uint32_t st[8];
+  sha256_iv(st);
+  ShaPacker p;
+  int widx = 0;  // whole words in the column
+  const uint32_t* no_tokens = nullptr;  // items 0..3 and n + 4.. read none
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 4; ++k) {
+    int len;
+    const uint64_t item = sha_chunk_item(k, parent, no_tokens, n, &len);
+    sha_seg_put(p, buf, widx, item, len);
+  }
+  const int full = n / SEG;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int s = 0; s <= full; ++s) {
+    const bool last = s == full;
+    const int cnt = last ? n - full * SEG : SEG;
+    uint32_t tok[SEG];
+    load(s * SEG, cnt, tok);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < SEG; ++j) {
+      // not a break: a loop with an early exit is not unrolled, and a
+      // rolled one indexes tok[] by a register
+      if (j < cnt) {
+        int len;
+        const uint64_t item = sha_cbor_u32_item(tok[j], 0, &len);
+        sha_seg_put(p, buf, widx, item, len);
+      }
+    }
+    int nblk = widx >> 4;  // whole blocks in the column
+    if (last) {
+      for (int k = n + 4; k < n + 6; ++k) {  // null, 0x80
+        int len;
+        const uint64_t item = sha_chunk_item(k, parent, no_tokens, n, &len);
+        sha_seg_put(p, buf, widx, item, len);
+      }
+      // a partial word is already in place at widx (ShaPacker)
+      const int end = widx + (p.fill ? 1 : 0);
+      nblk = (end + 2 + 15) >> 4;
+      // zeros up to the low length word: at most 16 of them
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int i = 0; i < 16; ++i)
+        if (end + i < nblk * 16 - 1) buf.st(end + i, 0u);
+      buf.st(nblk * 16 - 1, (uint32_t)(p.nbytes - 1) * 8u);  // without 0x80
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int blk = 0; blk < max_blocks; ++blk) {
+      const bool mine = blk < nblk;
+      if (!any(active && mine)) break;
+      uint32_t w[16], nx[8];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int i = 0; i < 16; ++i) w[i] = buf.ld(blk * 16 + i);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int i = 0; i < 8; ++i) nx[i] = st[i];
+      sha256_compress(nx, w);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int i = 0; i < 8; ++i) st[i] = mine ? nx[i] : st[i];
+    }
+    if (!last) {
+      // the incomplete block to the front: its whole words, and whatever
+      // lies behind them, which the next puts overwrite (the pending bytes
+      // are in the packer and come back with the next put)
+      uint32_t w[16];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int i = 0; i < 16; ++i) w[i] = buf.ld(nblk * 16 + i);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int i = 0; i < 16; ++i) buf.st(i, w[i]);
+      widx &= 15;
+    }
+  }
+  uint64_t out = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 8; i += 2)
+    if (i == digest_word) out = ((uint64_t)st[i] << 32) | st[i + 1];
+  return out;
+}
 
 // Compile-time chain policy used by the kernels and host ops.
 template <int ALGO, typename TokT>

@@ -31,6 +31,15 @@ std::vector<uint64_t> tokens_to_chunk_hashes_fast(std::vector<uint64_t> tokens,
                                                   uint64_t parent,
                                                   int64_t block_size,
                                                   int64_t algo);
+// Twin of the stream chain kernels (hip_ops.hip k_*_chain_stream), which
+// take the block size at run time: 1 <= block_size <= 65535, a tokens-array
+// header of at most three bytes.  In every build.
+inline bool stream_chain_block_size_ok(int64_t block_size) {
+  return block_size >= 1 && block_size <= 0xFFFF;
+}
+std::vector<uint64_t> tokens_to_chunk_hashes_stream(
+    std::vector<uint64_t> tokens, uint64_t parent, int64_t block_size,
+    int64_t algo);
 std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
                                          at::Tensor parents,
                                          int64_t block_size, int64_t algo);
