@@ -139,15 +139,33 @@ class WriteRoute:
     tokens_int32: bool  # tokens go up as int32 bits (uint32 token ids)
 
 
-def plan_write_route(flat: FlatEvents, block_size: int) -> WriteRoute:
+EVENT_CHAIN_LAYOUTS = ("rect", "waves")
+# the stream chain kernels: a tokens-array header of at most three bytes
+WAVES_MAX_BLOCK_SIZE = 65535
+
+
+def check_event_chain_layout(layout: str) -> str:
+    if layout not in EVENT_CHAIN_LAYOUTS:
+        raise ValueError(
+            f"event_chain_layout must be one of {EVENT_CHAIN_LAYOUTS}, "
+            f"not {layout!r}")
+    return layout
+
+
+def plan_write_route(flat: FlatEvents, block_size: int,
+                     layout: str = "rect") -> WriteRoute:
     """Kernel selection, from host-side data only:
      - serial wave-per-group kernel when a burst both stores AND removes
        some engine hash (per-pod op order matters);
-     - lane-per-EVENT transposed-chain kernel when no event's parent is
-       another event of THIS burst (parents resolve via the engine map):
-       8x the chain parallelism, coalesced int32 token loads, HALF the
-       upload; the transpose runs on-device (numpy: ~2-5 ms/batch);
+     - lane-per-EVENT chain kernel when no event's parent is another event
+       of THIS burst (parents resolve via the engine map): 8x the chain
+       parallelism, coalesced int32 token loads, HALF the upload.  Under
+       layout "rect" this is the transposed-chain kernel over one token
+       rectangle [max_tokens, E], at block sizes up to 64 (the transpose
+       runs on-device; numpy: ~2-5 ms/batch); under "waves" the wave-tiled
+       chain over per-wave token images, at block sizes 1..65535;
      - lane-per-group phase-split kernel otherwise."""
+    check_event_chain_layout(layout)
     if flat.ev_type.any():
         stored, removed = set(), set()
         eh_list = flat.ehashes.tolist()
@@ -156,11 +174,14 @@ def plan_write_route(flat: FlatEvents, block_size: int) -> WriteRoute:
             (removed if t else stored).update(eh_list[eh_off[e]:eh_off[e + 1]])
         if stored & removed:
             return WriteRoute("gpu_apply_events", 0, False)
-    use_tr = block_size <= 64
-    if use_tr and flat.has_parent.any():
+    waves = layout == "waves" and 1 <= block_size <= WAVES_MAX_BLOCK_SIZE
+    per_event = waves or block_size <= 64
+    if per_event and flat.has_parent.any():
         par = flat.parents[flat.has_parent.astype(bool)]
-        use_tr = not np.isin(par, flat.ehashes).any()
-    if not use_tr:
+        per_event = not np.isin(par, flat.ehashes).any()
+    if not per_event:
         return WriteRoute("gpu_apply_events_split", 0, False)
+    if waves:
+        return WriteRoute("gpu_apply_events_split_waves", 0, True)
     return WriteRoute("gpu_apply_events_split_tr",
                       max(1, int(np.diff(flat.tok_off).max())), True)

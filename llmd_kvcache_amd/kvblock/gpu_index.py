@@ -33,8 +33,8 @@ import torch
 from ..scorer import default_kv_cache_backend_configs
 from ..utils import hashing
 from ..utils.idgate import IdGate
-from .event_batch import (FIELDS, FlatEvents, flatten_event_batches,
-                          plan_write_route)
+from .event_batch import (FIELDS, FlatEvents, check_event_chain_layout,
+                          flatten_event_batches, plan_write_route)
 from .index import Index
 from .keys import Key, PodEntry
 
@@ -254,6 +254,15 @@ class TableIndexConfig:
     tier_names: List[str] = field(
         default_factory=lambda: [b.name for b in default_kv_cache_backend_configs()]
     )
+    # token layout of the write path's lane-per-event chain on a GPU table:
+    # "rect" stages one rectangle [longest event, E] and serves block sizes
+    # up to 64 (gpu_apply_events_split_tr); "waves" sorts the events by
+    # chain length into waves of 64 with a token image each and serves
+    # block sizes 1..65535 (gpu_apply_events_split_waves)
+    event_chain_layout: str = "rect"
+
+    def __post_init__(self):
+        check_event_chain_layout(self.event_chain_layout)
 
 
 @dataclass
@@ -473,6 +482,8 @@ class TableIndex(Index):
     def __init__(self, cfg: Optional[TableIndexConfig] = None,
                  registry: Optional[Registry] = None):
         self.cfg = cfg or TableIndexConfig()
+        # again here: a dict/JSON overlay sets fields after construction
+        check_event_chain_layout(self.cfg.event_chain_layout)
         self.table = KvTable(self.cfg)
         self.registry = registry or Registry(self.cfg.tier_names)
         self._write_lock = threading.Lock()  # CPU ops are single-writer
@@ -957,9 +968,15 @@ def _upload_events(flat: FlatEvents, route, up, device) -> FlatEvents:
         # flat, so it lives until after the launch like every other array.
         flat.tokens = flat.tokens.astype(np.uint32).view(np.int32)
     dev = FlatEvents()
+    # the waves op plans from tok_off, eh_off and ev_type on the host and
+    # uploads them with its plan; it has no use for the groups
+    host = (("tok_off", "eh_off", "ev_type", "grp_off")
+            if route.op == "gpu_apply_events_split_waves" else ())
     for name in FIELDS:
-        setattr(dev, name, up.up(getattr(flat, name), name, device,
-                                 wait=name not in ("tokens", "ehashes")))
+        arr = getattr(flat, name)
+        setattr(dev, name, torch.from_numpy(arr) if name in host else
+                up.up(arr, name, device,
+                      wait=name not in ("tokens", "ehashes")))
     if route.op != "gpu_apply_events":
         flat.ev_of = flat.event_of_hash()
         dev.ev_of = up.up(flat.ev_of, "ev_of", device)
@@ -1060,7 +1077,8 @@ class GpuIndex(TableIndex):
         if flat is None:
             return
         block_size = token_processor.block_size
-        route = plan_write_route(flat, block_size)
+        route = plan_write_route(flat, block_size,
+                                 self.cfg.event_chain_layout)
         up = _event_uploader(self)
         up.begin()
         d = _upload_events(flat, route, up, self.device)
@@ -1075,6 +1093,9 @@ class GpuIndex(TableIndex):
         elif route.op == "gpu_apply_events_split":
             t.ops.gpu_apply_events_split(*head, d.grp_off, d.ev_of,
                                          d.model_of, *tail, algo_id)
+        elif route.op == "gpu_apply_events_split_waves":
+            t.ops.gpu_apply_events_split_waves(*head, d.ev_of, d.model_of,
+                                               *tail, algo_id)
         else:
             t.ops.gpu_apply_events_split_tr(*head, d.ev_of, d.model_of, *tail,
                                             route.max_tokens, algo_id)

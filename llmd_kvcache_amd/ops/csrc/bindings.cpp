@@ -26,6 +26,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("algo") = 0);
   m.def("plan_ragged_waves", &kvidx::plan_ragged_waves_op, py::arg("tokens"),
         py::arg("offsets"), py::arg("block_size"));
+  m.def("plan_event_waves", &kvidx::plan_event_waves_op, py::arg("tok_off"),
+        py::arg("eh_off"), py::arg("ev_type"), py::arg("block_size"));
   m.def("cpu_insert", &kvidx::cpu_insert);
   m.def("cpu_compact", &kvidx::cpu_compact);
   m.def("cpu_evict", &kvidx::cpu_evict);
@@ -151,6 +153,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ev_of"), py::arg("model_of"), py::arg("init_hash_bits"),
         py::arg("block_size"), py::arg("epoch"), py::arg("shard_id"),
         py::arg("num_shards"), py::arg("max_tokens"), py::arg("algo") = 0);
+  // plan + upload + stage + chain + inserts; the GIL is released for all
+  m.def("gpu_apply_events_split_waves", &kvidx::gpu_apply_events_split_waves,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("tok_off"),
+        py::arg("ehashes"), py::arg("eh_off"), py::arg("parents"),
+        py::arg("has_parent"), py::arg("ev_type"), py::arg("pod_entry"),
+        py::arg("ev_of"), py::arg("model_of"), py::arg("init_hash_bits"),
+        py::arg("block_size"), py::arg("epoch"), py::arg("shard_id"),
+        py::arg("num_shards"), py::arg("algo") = 0,
+        py::call_guard<py::gil_scoped_release>());
 #else
   m.attr("HAS_HIP") = false;
 #endif

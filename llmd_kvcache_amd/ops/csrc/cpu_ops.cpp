@@ -283,6 +283,23 @@ std::vector<at::Tensor> kvidx::plan_ragged_waves_op(at::Tensor tokens,
           p.i32(p.host, p.at_h_off(), p.B + 1)};
 }
 
+std::vector<at::Tensor> kvidx::plan_event_waves_op(at::Tensor tok_off,
+                                                   at::Tensor eh_off,
+                                                   at::Tensor ev_type,
+                                                   int64_t block_size) {
+  // no tensors to bound the offsets by: the arrays' own last entries
+  TORCH_CHECK(tok_off.numel() >= 1 && eh_off.numel() >= 1,
+              "tok_off and eh_off must hold E + 1 offsets");
+  const WavePlan p = plan_event_waves(
+      tok_off, eh_off, ev_type, tok_off[-1].item<int64_t>(),
+      eh_off[-1].item<int64_t>(), block_size);
+  return {p.i32(p.host, p.at_perm(), 64 * p.G),
+          p.i32(p.host, p.at_wave_k(), p.G), p.img_off(p.host),
+          p.i32(p.host, p.at_tile_start(), p.G + 1),
+          p.i32(p.host, p.at_h_off(), p.B + 1),
+          p.i32(p.host, p.at_n_chunks(), p.B)};
+}
+
 // Tombstone compaction (ROADMAP #9): rehash every live entry of `old`
 // into the freshly-zeroed `nw` bundle (optionally a different power-of-
 // two capacity). Stamps (approximate-LRU epochs) and pod rows are

@@ -2147,17 +2147,49 @@ DEV void chain_flush_csr(const uint64_t* stage, uint64_t* __restrict__ out,
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Chain root policies of the four wave chain kernels: where lane l's chain
+// starts.  Each kernel is one body under two __global__ entries, as
+// fused_score_body is under its epilogues.  root(p, mc) is called once per
+// lane in the prologue, with the lane's row p of the plan (-1: none) and
+// its chunk count, and is over before the chunk loop, so the loop is the
+// same convergent one under either policy.
+//
+// RootInit: one constant for the whole batch - the read path, where every
+// prompt hashes from the chain root.
+struct RootInit {
+  uint64_t init;
+  DEV uint64_t operator()(int, int) const { return init; }
+};
+
+// RootEvents: the rows are events, and event e starts from the request key
+// its parent engine hash maps to in the engine map (dev_event_parent), else
+// from init.  One divergent probe per chain: no launch and no roots buffer
+// of its own.  Lanes without a chunk do not probe.  An engine-map value may
+// be below 2^32; the FNV bodies' `wide` vote sees it from chunk 0 on, since
+// it votes on h before every chunk.
+struct RootEvents {
+  Table v;
+  const uint64_t* __restrict__ parents;    // [E]
+  const uint8_t* __restrict__ has_parent;  // [E]
+  const int32_t* __restrict__ model_of;    // [E]
+  uint64_t init;
+  DEV uint64_t operator()(int e, int mc) const {
+    if (mc <= 0) return init;
+    return dev_event_parent(v, has_parent, parents, model_of, e, init);
+  }
+};
+
 // k_fnv_chain_tr's chunk body over wave g's own image, wave_k[g] trips.
 // One-wave workgroups, block g = wave g: the longest waves are dispatched
 // first.  Lane l is prompt perm[64 g + l]; -1 is a chain of no chunks.
 // out: CSR, chunk c of prompt p at out[h_off[p] + c]; nothing outside
 // [0, total_chunks) is written.
-template <int BS>
-__global__ void __launch_bounds__(64) k_fnv_chain_waves(
+template <int BS, typename Root>
+DEV void fnv_chain_waves_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    uint64_t init, uint64_t* __restrict__ out) {
+    Root root, uint64_t* __restrict__ out) {
   __shared__ uint64_t stage[64 * CHAIN_STAGE_ROW];
   const int g = blockIdx.x;
   const int wl = threadIdx.x;
@@ -2167,7 +2199,7 @@ __global__ void __launch_bounds__(64) k_fnv_chain_waves(
   const int ho = h_off[pc];
   const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
   const int32_t* tokens_t = img + img_off[g] + wl;
-  uint64_t h = init;
+  uint64_t h = root(p, mc);
   for (int c = 0; c < K; ++c) {
     uint32_t tok[BS];
 #pragma unroll
@@ -2184,17 +2216,39 @@ __global__ void __launch_bounds__(64) k_fnv_chain_waves(
   }
 }
 
+template <int BS>
+__global__ void __launch_bounds__(64) k_fnv_chain_waves(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    uint64_t init, uint64_t* __restrict__ out) {
+  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off,
+                           RootInit{init}, out);
+}
+
+// The ingest entry: rows are events, h_off is the events' eh_off and out
+// is req_scratch, of which only the chunks of kept stores are written.
+template <int BS>
+__global__ void __launch_bounds__(64) k_fnv_chain_waves_ev(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    RootEvents roots, uint64_t* __restrict__ out) {
+  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off, roots,
+                           out);
+}
+
 // k_sha_chain_tr over the per-wave images: wave_k[g] as the loop bound,
 // CSR stores of active chunks only, no zero-fill tail.  The waves of a
 // workgroup have different trip counts, which is safe: nothing in
 // chunk_hash_sha256_wave is a workgroup barrier (each lane packs into its
 // own LDS column, the votes are wave-wide), and neither is anything here.
-template <int BS, int ALGO>
-__global__ void k_sha_chain_waves(
+template <int BS, int ALGO, typename Root>
+DEV void sha_chain_waves_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    int G, uint64_t init, uint64_t* __restrict__ out) {
+    int G, Root root, uint64_t* __restrict__ out) {
   constexpr int NT = sha_tr_threads(BS);
   __shared__ uint32_t sha_words[sha_tr_words(BS) * NT];
   const int wl = threadIdx.x & 63;
@@ -2208,7 +2262,7 @@ __global__ void k_sha_chain_waves(
   const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
   const int32_t* tokens_t = img + img_off[g] + wl;
   ShaLdsCol<NT> col{sha_words + threadIdx.x};
-  uint64_t h = init;
+  uint64_t h = root(p, mc);
   for (int c = 0; c < K; ++c) {
     const bool active = c < mc;
     uint32_t tok[BS];
@@ -2220,6 +2274,26 @@ __global__ void k_sha_chain_waves(
     h = active ? h2 : h;
     if (active) o[c] = h;
   }
+}
+
+template <int BS, int ALGO>
+__global__ void k_sha_chain_waves(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int G, uint64_t init, uint64_t* __restrict__ out) {
+  sha_chain_waves_body<BS, ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+                                 G, RootInit{init}, out);
+}
+
+template <int BS, int ALGO>
+__global__ void k_sha_chain_waves_ev(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int G, RootEvents roots, uint64_t* __restrict__ out) {
+  sha_chain_waves_body<BS, ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+                                 G, roots, out);
 }
 
 // ---------------------------------------------------------------------
@@ -2240,11 +2314,12 @@ __global__ void k_sha_chain_waves(
 // steps - one group of block_size % 16, chunk_hash_end.  The image is
 // position-major, so the walk over a wave's rows is one running pointer
 // from the first chunk to the last.
-__global__ void __launch_bounds__(64) k_fnv_chain_stream(
+template <typename Root>
+DEV void fnv_chain_stream_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    uint64_t init, int block_size, uint64_t* __restrict__ out) {
+    Root root, int block_size, uint64_t* __restrict__ out) {
   __shared__ uint64_t stage[64 * CHAIN_STAGE_ROW];
   const int g = blockIdx.x;
   const int wl = threadIdx.x;
@@ -2255,7 +2330,7 @@ __global__ void __launch_bounds__(64) k_fnv_chain_stream(
   const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
   const ChainShape s = chain_shape(block_size);
   const int32_t* t = img + img_off[g] + wl;  // rows [0, K * block_size)
-  uint64_t h = init;
+  uint64_t h = root(p, mc);
   for (int c = 0; c < K; ++c) {
     const bool active = c < mc;
     const bool wide = __all(!active || h > 0xFFFFFFFFull);
@@ -2284,6 +2359,24 @@ __global__ void __launch_bounds__(64) k_fnv_chain_stream(
   }
 }
 
+__global__ void __launch_bounds__(64) k_fnv_chain_stream(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    uint64_t init, int block_size, uint64_t* __restrict__ out) {
+  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off,
+                        RootInit{init}, block_size, out);
+}
+
+__global__ void __launch_bounds__(64) k_fnv_chain_stream_ev(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    RootEvents roots, int block_size, uint64_t* __restrict__ out) {
+  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off, roots,
+                        block_size, out);
+}
+
 // SHA-256 over the same payload: chunk_hash_sha256_seg, SHA_SEG_TOKENS
 // tokens at a time through a column of sha_seg_words() words per lane
 // (28 KB for the wave, whatever the block size).  A segment's tokens are
@@ -2292,12 +2385,12 @@ __global__ void __launch_bounds__(64) k_fnv_chain_stream(
 // under which sit up to five compressions.  One-wave workgroups as the FNV
 // kernel: there is no workgroup barrier here or in the driver, and a wave
 // with fewer trips holds no other wave's LDS.
-template <int ALGO>
-__global__ void __launch_bounds__(64) k_sha_chain_stream(
+template <int ALGO, typename Root>
+DEV void sha_chain_stream_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    uint64_t init, int block_size, uint64_t* __restrict__ out) {
+    Root root, int block_size, uint64_t* __restrict__ out) {
   constexpr int SEG = SHA_SEG_TOKENS;
   __shared__ uint32_t sha_words[sha_seg_words(SEG) * 64];
   const int g = blockIdx.x;
@@ -2309,7 +2402,7 @@ __global__ void __launch_bounds__(64) k_sha_chain_stream(
   const int K = __builtin_amdgcn_readfirstlane(wave_k[g]);
   const int32_t* chunk = img + img_off[g] + wl;  // rows [0, K * block_size)
   ShaLdsCol<64> col{sha_words + wl};
-  uint64_t h = init;
+  uint64_t h = root(p, mc);
   for (int c = 0; c < K; ++c, chunk += (int64_t)block_size * 64) {
     const bool active = c < mc;
     auto load = [chunk](int first, int cnt, uint32_t (&tok)[SEG])
@@ -2329,6 +2422,26 @@ __global__ void __launch_bounds__(64) k_sha_chain_stream(
     h = active ? h2 : h;
     if (active) o[c] = h;
   }
+}
+
+template <int ALGO>
+__global__ void __launch_bounds__(64) k_sha_chain_stream(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    uint64_t init, int block_size, uint64_t* __restrict__ out) {
+  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+                              RootInit{init}, block_size, out);
+}
+
+template <int ALGO>
+__global__ void __launch_bounds__(64) k_sha_chain_stream_ev(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    RootEvents roots, int block_size, uint64_t* __restrict__ out) {
+  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+                              roots, block_size, out);
 }
 
 template <int ALGO>
@@ -3273,11 +3386,94 @@ std::vector<at::Tensor> kvidx::gpu_topk_flat_tokens(
                              n_tiers, top_n);
 }
 
-// The ragged device chain: plan (host) -> one upload -> k_stage_ragged_waves
-// -> k_*_chain_waves, on the current stream.  hashes int64 [total_chunks]
-// and h_off int32 [B+1] on `dev`; both undefined where the batch has no
-// whole chunk (nothing is uploaded or launched then).
+// Stage and chain over an uploaded wave plan, for the read path's prompts
+// (roots: the batch's one init, uint64_t) and the write path's events
+// (roots: RootEvents): k_stage_ragged_waves, then the templated chain
+// kernel at block sizes 4/8/16/32/64 and the stream kernel at every other,
+// under the entry the roots select.  up: p.host on the device; tok: flat
+// tokens on the device, int64 or int32; out: int64, chunk c of row r at
+// h_off[r] + c.  p.G > 0.  Everything on the current stream.
 namespace kvidx {
+template <typename Roots>
+static void launch_wave_chain(const WavePlan& p, const at::Tensor& up,
+                              const at::Tensor& tok, int64_t block_size,
+                              int64_t algo, Roots roots,
+                              const at::Tensor& out) {
+  constexpr bool EV = std::is_same_v<Roots, RootEvents>;
+  const at::Tensor img_off = p.img_off(up);
+  const int32_t* w = i32p(up);
+  const int32_t* n_chunks = w + p.at_n_chunks();
+  const int32_t* perm = w + p.at_perm();
+  const int32_t* wave_k = w + p.at_wave_k();
+  const int32_t* h_off = w + p.at_h_off();
+  auto img = at::empty({p.image_elems}, up.options());
+  const int G = (int)p.G;
+  auto stage = [&](auto* flat) {
+    using TokT = std::remove_const_t<std::remove_pointer_t<decltype(flat)>>;
+    hipLaunchKernelGGL(k_stage_ragged_waves<TokT>, dim3((unsigned)p.tiles),
+                       dim3(256), 0, STREAM, flat, w + p.at_tok_off(),
+                       n_chunks, perm, wave_k, img_off.data_ptr<int64_t>(),
+                       w + p.at_tile_start(), G, (int)block_size, i32p(img));
+  };
+  if (tok.dtype() == at::kLong)
+    stage(tok.data_ptr<int64_t>());
+  else
+    stage(tok.data_ptr<int32_t>());
+  if (!chain_block_size_templated(block_size)) {
+    // one-wave workgroups, block g = wave g, for either hash
+    dispatch_algo(algo, [&](auto A) {
+      constexpr int AL = decltype(A)::value;
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64), 0, STREAM,
+                           i32p(img), img_off.data_ptr<int64_t>(), perm,
+                           wave_k, n_chunks, h_off, roots, (int)block_size,
+                           u64p(out));
+      };
+      if constexpr (AL == ALGO_FNV64A)
+        launch([] {
+          if constexpr (EV) return k_fnv_chain_stream_ev;
+          else return k_fnv_chain_stream;
+        }());
+      else
+        launch([] {
+          if constexpr (EV) return k_sha_chain_stream_ev<AL>;
+          else return k_sha_chain_stream<AL>;
+        }());
+    });
+    return;
+  }
+  dispatch_algo(algo, [&](auto A) {
+    dispatch_chain_block_size(block_size, [&](auto S) {
+      constexpr int AL = decltype(A)::value;
+      constexpr int BS = decltype(S)::value;
+      if constexpr (AL == ALGO_FNV64A) {
+        auto kern = [] {
+          if constexpr (EV) return k_fnv_chain_waves_ev<BS>;
+          else return k_fnv_chain_waves<BS>;
+        }();
+        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64), 0, STREAM,
+                           i32p(img), img_off.data_ptr<int64_t>(), perm,
+                           wave_k, n_chunks, h_off, roots, u64p(out));
+      } else {
+        constexpr int NT = sha_tr_threads(BS);
+        auto kern = [] {
+          if constexpr (EV) return k_sha_chain_waves_ev<BS, AL>;
+          else return k_sha_chain_waves<BS, AL>;
+        }();
+        hipLaunchKernelGGL(kern,
+                           dim3((unsigned)((G + NT / 64 - 1) / (NT / 64))),
+                           dim3(NT), 0, STREAM, i32p(img),
+                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
+                           h_off, G, roots, u64p(out));
+      }
+    });
+  });
+}
+
+// The ragged device chain: plan (host) -> one upload -> launch_wave_chain,
+// on the current stream.  hashes int64 [total_chunks] and h_off int32
+// [B+1] on `dev`; both undefined where the batch has no whole chunk
+// (nothing is uploaded or launched then).
 struct ChainedCsr {
   WavePlan p;
   at::Tensor hashes, h_off;
@@ -3291,75 +3487,20 @@ static ChainedCsr chain_ragged_waves(const at::Tensor& tokens_flat,
   // the five block sizes of the templated kernels keep them; every other
   // one the stream kernels take goes to those.  Refused before anything
   // is uploaded or launched.
-  const bool templated = chain_block_size_templated(block_size);
-  TORCH_CHECK(templated || stream_chain_block_size_ok(block_size),
+  TORCH_CHECK(chain_block_size_templated(block_size) ||
+                  stream_chain_block_size_ok(block_size),
               "the ragged device chain takes block sizes 1..65535");
   ChainedCsr c;
   c.p = plan_ragged_waves(tokens_flat, offsets, block_size);
   const WavePlan& p = c.p;
   if (p.G == 0) return c;
   const at::Tensor up = p.host.to(dev);
-  const at::Tensor img_off = p.img_off(up);
-  const int32_t* w = i32p(up);
-  const int32_t* n_chunks = w + p.at_n_chunks();
-  const int32_t* perm = w + p.at_perm();
-  const int32_t* wave_k = w + p.at_wave_k();
   c.h_off = p.i32(up, p.at_h_off(), p.B + 1);
-  auto img = at::empty({p.image_elems}, up.options());
   c.hashes = at::empty({p.total_chunks}, up.options().dtype(at::kLong));
   auto tok = tokens_flat.is_cuda() ? tokens_flat.contiguous()
                                    : tokens_flat.contiguous().to(dev);
-  const int G = (int)p.G;
-  auto stage = [&](auto* flat) {
-    using TokT = std::remove_const_t<std::remove_pointer_t<decltype(flat)>>;
-    hipLaunchKernelGGL(k_stage_ragged_waves<TokT>, dim3((unsigned)p.tiles),
-                       dim3(256), 0, STREAM, flat, w + p.at_tok_off(),
-                       n_chunks, perm, wave_k, img_off.data_ptr<int64_t>(),
-                       w + p.at_tile_start(), G, (int)block_size, i32p(img));
-  };
-  if (tok.dtype() == at::kLong)
-    stage(tok.data_ptr<int64_t>());
-  else
-    stage(tok.data_ptr<int32_t>());
-  if (!templated) {
-    // one-wave workgroups, block g = wave g, for either hash
-    dispatch_algo(algo, [&](auto A) {
-      constexpr int AL = decltype(A)::value;
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64), 0, STREAM,
-                           i32p(img), img_off.data_ptr<int64_t>(), perm,
-                           wave_k, n_chunks, i32p(c.h_off),
-                           (uint64_t)init_hash_bits, (int)block_size,
-                           u64p(c.hashes));
-      };
-      if constexpr (AL == ALGO_FNV64A)
-        launch(k_fnv_chain_stream);
-      else
-        launch(k_sha_chain_stream<AL>);
-    });
-    return c;
-  }
-  dispatch_algo(algo, [&](auto A) {
-    dispatch_chain_block_size(block_size, [&](auto S) {
-      constexpr int AL = decltype(A)::value;
-      constexpr int BS = decltype(S)::value;
-      if constexpr (AL == ALGO_FNV64A) {
-        hipLaunchKernelGGL(k_fnv_chain_waves<BS>, dim3((unsigned)G), dim3(64),
-                           0, STREAM, i32p(img), img_off.data_ptr<int64_t>(),
-                           perm, wave_k, n_chunks, i32p(c.h_off),
-                           (uint64_t)init_hash_bits, u64p(c.hashes));
-      } else {
-        constexpr int NT = sha_tr_threads(BS);
-        auto kern = k_sha_chain_waves<BS, AL>;  // one macro argument
-        hipLaunchKernelGGL(kern,
-                           dim3((unsigned)((G + NT / 64 - 1) / (NT / 64))),
-                           dim3(NT), 0, STREAM, i32p(img),
-                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
-                           i32p(c.h_off), G, (uint64_t)init_hash_bits,
-                           u64p(c.hashes));
-      }
-    });
-  });
+  launch_wave_chain(p, up, tok, block_size, algo, (uint64_t)init_hash_bits,
+                    c.hashes);
   return c;
 }
 }  // namespace kvidx
@@ -3485,6 +3626,63 @@ void kvidx::gpu_apply_events_split_tr(KVIDX_TABLE_PARAMS,
   launch_event_inserts(v, ehashes, eh_off, ev_of, ev_type, tok_off, pod_entry,
                        model_of, block_size, epoch, shard_id, num_shards,
                        req_scratch);
+}
+
+// Wave-tiled phase-split apply: the _tr route's bursts (no batch-local
+// parent, no store+remove conflict; host verified) over per-wave token
+// images, at any block size.  Events sorted by chain length share waves, a
+// wave's image is as tall as its own longest event, and each lane resolves
+// its parent in the chain kernel's prologue (RootEvents).  The chain
+// kernels write only the chunks of kept stores, which are all that
+// k_event_inserts reads of req_scratch, so it is not cleared.
+void kvidx::gpu_apply_events_split_waves(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor tok_off,
+    at::Tensor ehashes, at::Tensor eh_off, at::Tensor parents,
+    at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
+    at::Tensor ev_of, at::Tensor model_of, int64_t init_hash_bits,
+    int64_t block_size, int64_t epoch, int64_t shard_id, int64_t num_shards,
+    int64_t algo) {
+  // refused before anything is uploaded or launched
+  TORCH_CHECK(stream_chain_block_size_ok(block_size),
+              "the wave-tiled ingest chain takes block sizes 1..65535");
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  const at::Device dev = keys.device();
+  const auto on_dev = [&](const at::Tensor& t, at::ScalarType ty, int64_t n) {
+    return t.device() == dev && t.dtype() == ty && t.is_contiguous() &&
+           t.numel() == n;
+  };
+  const int64_t E = ev_type.numel();
+  const int64_t n = ehashes.numel();
+  TORCH_CHECK(on_dev(tokens_flat, at::kInt, tokens_flat.numel()),
+              "event tokens must be int32 (uint32 bit pattern) on the "
+              "table's device");
+  TORCH_CHECK(on_dev(ehashes, at::kLong, n) && on_dev(ev_of, at::kInt, n),
+              "ehashes int64 and ev_of int32 must hold one entry per hash "
+              "on the table's device");
+  TORCH_CHECK(on_dev(parents, at::kLong, E) &&
+                  on_dev(has_parent, at::kByte, E) &&
+                  on_dev(pod_entry, at::kInt, E) &&
+                  on_dev(model_of, at::kInt, E),
+              "parents, has_parent, pod_entry and model_of must hold one "
+              "entry per event on the table's device");
+  const WavePlan p = plan_event_waves(tok_off, eh_off, ev_type,
+                                      tokens_flat.numel(), n, block_size);
+  if (E == 0 || n == 0) return;
+  const at::Tensor up = p.host.to(dev);  // the one upload
+  const at::Tensor d_tok_off = p.i32(up, p.at_tok_off(), E + 1);
+  const at::Tensor d_eh_off = p.i32(up, p.at_h_off(), E + 1);
+  const at::Tensor d_ev_type =
+      p.i32(up, p.at_tail(), p.tail).view(at::kByte).slice(0, 0, E);
+  auto req_scratch = at::empty({n}, ehashes.options());
+  if (p.G > 0)  // else only removals and dropped stores: the inserts alone
+    launch_wave_chain(p, up, tokens_flat, block_size, algo,
+                      RootEvents{v, u64p(parents), u8p(has_parent),
+                                 i32p(model_of), (uint64_t)init_hash_bits},
+                      req_scratch);
+  launch_event_inserts(v, ehashes, d_eh_off, ev_of, d_ev_type, d_tok_off,
+                       pod_entry, model_of, block_size, epoch, shard_id,
+                       num_shards, req_scratch);
 }
 
 // Phase-split apply: bmap build -> chains (lane per group) -> inserts

@@ -49,6 +49,13 @@ std::vector<at::Tensor> hash_chain_batch(at::Tensor tokens, at::Tensor offsets,
 std::vector<at::Tensor> plan_ragged_waves_op(at::Tensor tokens,
                                              at::Tensor offsets,
                                              int64_t block_size);
+// The host plan of the wave-tiled ingest chain (plan_event_waves below) as
+// CPU tensors: plan_ragged_waves_op's five, lanes = events, and n_chunks
+// int32 [E] as the sixth.  In every build.
+std::vector<at::Tensor> plan_event_waves_op(at::Tensor tok_off,
+                                            at::Tensor eh_off,
+                                            at::Tensor ev_type,
+                                            int64_t block_size);
 
 // ---- table ops, CPU (cpu_ops.cpp) ------------------------------------
 void cpu_insert(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
@@ -299,6 +306,23 @@ void gpu_apply_events_split_tr(KVIDX_TABLE_PARAMS, at::Tensor tokens_flat,
                                int64_t block_size, int64_t epoch,
                                int64_t shard_id, int64_t num_shards,
                                int64_t max_tokens, int64_t algo);
+// The wave-tiled ingest chain: gpu_apply_events_split_tr's bursts (no
+// batch-local parent, no store+remove conflict; host verified) at any block
+// size 1..65535 and without the [max_tokens, E] rectangle.  tokens_flat
+// int32 on the device; tok_off, eh_off and ev_type on the HOST (the plan
+// reads them, and their device copies ride the plan's one upload); the
+// rest on the device.  plan_event_waves -> one upload ->
+// k_stage_ragged_waves -> the event-root entry of a wave chain kernel ->
+// k_event_inserts, on the current stream with no host wait in between.
+void gpu_apply_events_split_waves(KVIDX_TABLE_PARAMS, at::Tensor tokens_flat,
+                                  at::Tensor tok_off, at::Tensor ehashes,
+                                  at::Tensor eh_off, at::Tensor parents,
+                                  at::Tensor has_parent, at::Tensor ev_type,
+                                  at::Tensor pod_entry, at::Tensor ev_of,
+                                  at::Tensor model_of, int64_t init_hash_bits,
+                                  int64_t block_size, int64_t epoch,
+                                  int64_t shard_id, int64_t num_shards,
+                                  int64_t algo);
 #endif
 
 // ---- shared host helpers ---------------------------------------------
@@ -453,7 +477,7 @@ inline RaggedPlan plan_ragged(const at::Tensor& tokens,
 // wave_k > 0.
 // One int32 buffer, so that everything goes up in one copy:
 //   [img_off int64 (G+1) | n_chunks (B) | tok_off (B+1) | h_off (B+1) |
-//    perm (64 G) | wave_k (G) | tile_start (G+1)]
+//    perm (64 G) | wave_k (G) | tile_start (G+1) | tail]
 //  - perm[64 g + r]: the prompt in row r of wave g, -1 past the batch;
 //  - wave_k[g]: n_chunks of the wave's first prompt, its maximum;
 //  - img_off[g]: element offset of wave g's image, the sum of wave_k *
@@ -465,7 +489,8 @@ inline RaggedPlan plan_ragged(const at::Tensor& tokens,
 struct WavePlan {
   int64_t B = 0, G = 0, max_k = 0, total_chunks = 0;
   int64_t image_elems = 0, tiles = 0;
-  at::Tensor host;  // int32 [2 (G+1) + 3 B + 2 + 66 G + 1]
+  int64_t tail = 0;  // caller's int32 words behind tile_start
+  at::Tensor host;   // int32 [2 (G+1) + 3 B + 2 + 66 G + 1 + tail]
   int64_t at_img_off() const { return 0; }
   int64_t at_n_chunks() const { return 2 * (G + 1); }
   int64_t at_tok_off() const { return at_n_chunks() + B; }
@@ -473,7 +498,8 @@ struct WavePlan {
   int64_t at_perm() const { return at_h_off() + B + 1; }
   int64_t at_wave_k() const { return at_perm() + 64 * G; }
   int64_t at_tile_start() const { return at_wave_k() + G; }
-  int64_t words() const { return at_tile_start() + G + 1; }
+  int64_t at_tail() const { return at_tile_start() + G + 1; }
+  int64_t words() const { return at_tail() + tail; }
   // pieces of `buf`, the host buffer or its copy on the device
   at::Tensor i32(const at::Tensor& buf, int64_t at, int64_t n) const {
     return buf.slice(0, at, at + n);
@@ -483,22 +509,25 @@ struct WavePlan {
   }
 };
 
-inline WavePlan plan_ragged_waves(const at::Tensor& tokens,
-                                  const at::Tensor& offsets,
-                                  int64_t block_size) {
-  const RaggedPlan r = plan_ragged(tokens, offsets, block_size);
+// The wave half of a plan, shared by the prompt plan and the event plan:
+// r holds the lanes' n_chunks and tok_off; h_off_src is the lanes' h_off
+// [B+1], or null for the exclusive prefix sum of n_chunks; tail_words int32
+// words are left to the caller behind tile_start.
+inline WavePlan plan_waves(const RaggedPlan& r, int64_t block_size,
+                           const int32_t* h_off_src, int64_t tail_words) {
   const int32_t* nc = r.host.data_ptr<int32_t>();
   WavePlan p;
   p.B = r.B;
   p.max_k = r.max_k;
   p.total_chunks = r.total_chunks;
+  p.tail = tail_words;
   TORCH_CHECK(p.total_chunks <= INT32_MAX,
               "more than 2^31 - 1 chunks in one batch");
   std::vector<int32_t> order(p.B);
   for (int64_t b = 0; b < p.B; ++b) order[b] = (int32_t)b;
   std::stable_sort(order.begin(), order.end(),
                    [nc](int32_t a, int32_t b) { return nc[a] > nc[b]; });
-  int64_t live = 0;  // prompts with a whole chunk: they sort first
+  int64_t live = 0;  // lanes with a whole chunk: they sort first
   while (live < p.B && nc[order[live]] > 0) ++live;
   p.G = (live + 63) / 64;
   p.host = at::empty({p.words()}, at::kInt);
@@ -506,8 +535,12 @@ inline WavePlan plan_ragged_waves(const at::Tensor& tokens,
   int64_t* img_off = reinterpret_cast<int64_t*>(w);
   std::copy(nc, nc + 2 * p.B + 1, w + p.at_n_chunks());  // and tok_off
   int32_t* h_off = w + p.at_h_off();
-  h_off[0] = 0;
-  for (int64_t b = 0; b < p.B; ++b) h_off[b + 1] = h_off[b] + nc[b];
+  if (h_off_src) {
+    std::copy(h_off_src, h_off_src + p.B + 1, h_off);
+  } else {
+    h_off[0] = 0;
+    for (int64_t b = 0; b < p.B; ++b) h_off[b + 1] = h_off[b] + nc[b];
+  }
   int32_t* perm = w + p.at_perm();
   int32_t* wave_k = w + p.at_wave_k();
   int32_t* tile_start = w + p.at_tile_start();
@@ -525,6 +558,73 @@ inline WavePlan plan_ragged_waves(const at::Tensor& tokens,
   }
   p.image_elems = img_off[p.G];
   p.tiles = tile_start[p.G];
+  return p;
+}
+
+inline WavePlan plan_ragged_waves(const at::Tensor& tokens,
+                                  const at::Tensor& offsets,
+                                  int64_t block_size) {
+  return plan_waves(plan_ragged(tokens, offsets, block_size), block_size,
+                    nullptr, 0);
+}
+
+// Host half of the wave-tiled ingest chain (gpu_apply_events_split_waves):
+// plan_ragged_waves with EVENTS as lanes.  tok_off / eh_off int32 [E+1] and
+// ev_type uint8 [E] on the host, as FlatEvents holds them.
+//  - n_chunks[e] is event_chain_len's value (hip_ops.hip), and 0 for a
+//    BlockRemoved event and for a store whose engine-hash count differs
+//    from its whole chunks: those sort last and get no wave;
+//  - h_off[e] = eh_off[e], not a prefix sum of n_chunks: a removal or a
+//    dropped store still owns its engine hashes' slots, so chunk c of
+//    event e lies at eh_off[e] + c, where k_event_inserts reads it;
+//  - the tail behind tile_start is ev_type, E bytes in (E + 3) / 4 words,
+//    so that the one upload carries all k_event_inserts reads as well.
+// The stage kernel reads tokens[tok_off[e] + i] and the chain kernels write
+// out[eh_off[e] + c] unchecked, so both offset arrays are checked here
+// against n_tokens and n_hashes.
+inline WavePlan plan_event_waves(const at::Tensor& tok_off,
+                                 const at::Tensor& eh_off,
+                                 const at::Tensor& ev_type, int64_t n_tokens,
+                                 int64_t n_hashes, int64_t block_size) {
+  TORCH_CHECK(stream_chain_block_size_ok(block_size),
+              "the wave-tiled ingest chain takes block sizes 1..65535");
+  const auto host_1d = [](const at::Tensor& t, at::ScalarType ty) {
+    return t.device().is_cpu() && t.dtype() == ty && t.dim() == 1 &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(host_1d(tok_off, at::kInt) && host_1d(eh_off, at::kInt) &&
+                  host_1d(ev_type, at::kByte),
+              "tok_off / eh_off must be contiguous int32 and ev_type uint8 "
+              "host tensors");
+  const int64_t E = ev_type.numel();
+  TORCH_CHECK(tok_off.numel() == E + 1 && eh_off.numel() == E + 1,
+              "tok_off and eh_off must hold E + 1 offsets");
+  const int32_t* to = tok_off.data_ptr<int32_t>();
+  const int32_t* eo = eh_off.data_ptr<int32_t>();
+  const uint8_t* ty = ev_type.data_ptr<uint8_t>();
+  TORCH_CHECK(to[0] >= 0 && to[E] <= n_tokens,
+              "tok_off reaches outside the token tensor");
+  TORCH_CHECK(eo[0] >= 0 && eo[E] <= n_hashes,
+              "eh_off reaches outside the engine hashes");
+  RaggedPlan r;
+  r.B = E;
+  r.host = at::empty({2 * E + 1}, at::kInt);
+  int32_t* nc = r.host.data_ptr<int32_t>();
+  std::copy(to, to + E + 1, nc + E);
+  for (int64_t e = 0; e < E; ++e) {
+    TORCH_CHECK(to[e + 1] >= to[e] && eo[e + 1] >= eo[e],
+                "event offsets must not decrease");
+    const int64_t k = (to[e + 1] - to[e]) / block_size;
+    nc[e] = ty[e] != 1 && k == eo[e + 1] - eo[e] ? (int32_t)k : 0;
+    r.max_k = std::max<int64_t>(r.max_k, nc[e]);
+    r.total_chunks += nc[e];
+  }
+  const int64_t tail = (E + 3) / 4;
+  WavePlan p = plan_waves(r, block_size, eo, tail);
+  uint8_t* t8 = reinterpret_cast<uint8_t*>(p.host.data_ptr<int32_t>() +
+                                           p.at_tail());
+  std::fill(t8 + E, t8 + 4 * tail, (uint8_t)0);
+  std::copy(ty, ty + E, t8);
   return p;
 }
 
