@@ -139,9 +139,15 @@ class WriteRoute:
     tokens_int32: bool  # tokens go up as int32 bits (uint32 token ids)
 
 
-EVENT_CHAIN_LAYOUTS = ("rect", "waves")
+EVENT_CHAIN_LAYOUTS = ("rect", "waves", "linked")
 # the stream chain kernels: a tokens-array header of at most three bytes
 WAVES_MAX_BLOCK_SIZE = 65535
+# "linked" launches its chain kernel once per level of batch-local
+# parents; deeper bursts keep the lane-per-group kernel.  The value is the
+# depth sweep of profiles/r18_event_links.md: the deepest measured chain at
+# which the linked op's call was no slower than the lane-per-group op's
+# under both hashes (at 64 levels FNV is level to 0.4 % behind).
+EVENT_LINK_MAX_LEVELS = 32
 
 
 def check_event_chain_layout(layout: str) -> str:
@@ -153,7 +159,9 @@ def check_event_chain_layout(layout: str) -> str:
 
 
 def plan_write_route(flat: FlatEvents, block_size: int,
-                     layout: str = "rect") -> WriteRoute:
+                     layout: str = "rect", links=None,
+                     link_max_levels: int = EVENT_LINK_MAX_LEVELS
+                     ) -> WriteRoute:
     """Kernel selection, from host-side data only:
      - serial wave-per-group kernel when a burst both stores AND removes
        some engine hash (per-pod op order matters);
@@ -163,8 +171,13 @@ def plan_write_route(flat: FlatEvents, block_size: int,
        layout "rect" this is the transposed-chain kernel over one token
        rectangle [max_tokens, E], at block sizes up to 64 (the transpose
        runs on-device; numpy: ~2-5 ms/batch); under "waves" the wave-tiled
-       chain over per-wave token images, at block sizes 1..65535;
-     - lane-per-group phase-split kernel otherwise."""
+       chain over per-wave token images, at block sizes 1..65535, and
+       "linked" is "waves" here;
+     - lane-per-group phase-split kernel otherwise - except under "linked"
+       with links = (link, level, n_levels) as ops.plan_event_links gives
+       them for this burst: the linked wave chain, one chain launch per
+       level, where n_levels <= link_max_levels.  Without links, "linked"
+       routes as "waves"."""
     check_event_chain_layout(layout)
     if flat.ev_type.any():
         stored, removed = set(), set()
@@ -174,12 +187,16 @@ def plan_write_route(flat: FlatEvents, block_size: int,
             (removed if t else stored).update(eh_list[eh_off[e]:eh_off[e + 1]])
         if stored & removed:
             return WriteRoute("gpu_apply_events", 0, False)
-    waves = layout == "waves" and 1 <= block_size <= WAVES_MAX_BLOCK_SIZE
+    waves = (layout in ("waves", "linked")
+             and 1 <= block_size <= WAVES_MAX_BLOCK_SIZE)
     per_event = waves or block_size <= 64
     if per_event and flat.has_parent.any():
         par = flat.parents[flat.has_parent.astype(bool)]
         per_event = not np.isin(par, flat.ehashes).any()
     if not per_event:
+        if (waves and layout == "linked" and links is not None
+                and links[2] <= link_max_levels):
+            return WriteRoute("gpu_apply_events_split_linked", 0, True)
         return WriteRoute("gpu_apply_events_split", 0, False)
     if waves:
         return WriteRoute("gpu_apply_events_split_waves", 0, True)

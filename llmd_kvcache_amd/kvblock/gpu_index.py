@@ -33,8 +33,9 @@ import torch
 from ..scorer import default_kv_cache_backend_configs
 from ..utils import hashing
 from ..utils.idgate import IdGate
-from .event_batch import (FIELDS, FlatEvents, check_event_chain_layout,
-                          flatten_event_batches, plan_write_route)
+from .event_batch import (EVENT_LINK_MAX_LEVELS, FIELDS, FlatEvents,
+                          check_event_chain_layout, flatten_event_batches,
+                          plan_write_route)
 from .index import Index
 from .keys import Key, PodEntry
 
@@ -258,8 +259,15 @@ class TableIndexConfig:
     # "rect" stages one rectangle [longest event, E] and serves block sizes
     # up to 64 (gpu_apply_events_split_tr); "waves" sorts the events by
     # chain length into waves of 64 with a token image each and serves
-    # block sizes 1..65535 (gpu_apply_events_split_waves)
+    # block sizes 1..65535 (gpu_apply_events_split_waves); "linked" is
+    # "waves" plus the linked wave chain for bursts whose events chain from
+    # blocks of the same burst (gpu_apply_events_split_linked), which
+    # otherwise take the lane-per-group kernel under every layout
     event_chain_layout: str = "rect"
+    # "linked" only: the linked chain launches once per level of
+    # batch-local parents, so bursts deeper than this keep the
+    # lane-per-group kernel (profiles/r18_event_links.md)
+    event_link_max_levels: int = EVENT_LINK_MAX_LEVELS
 
     def __post_init__(self):
         check_event_chain_layout(self.event_chain_layout)
@@ -968,10 +976,11 @@ def _upload_events(flat: FlatEvents, route, up, device) -> FlatEvents:
         # flat, so it lives until after the launch like every other array.
         flat.tokens = flat.tokens.astype(np.uint32).view(np.int32)
     dev = FlatEvents()
-    # the waves op plans from tok_off, eh_off and ev_type on the host and
-    # uploads them with its plan; it has no use for the groups
+    # the waves ops plan from tok_off, eh_off and ev_type on the host and
+    # upload them with their plan; they have no use for the groups
     host = (("tok_off", "eh_off", "ev_type", "grp_off")
-            if route.op == "gpu_apply_events_split_waves" else ())
+            if route.op in ("gpu_apply_events_split_waves",
+                            "gpu_apply_events_split_linked") else ())
     for name in FIELDS:
         arr = getattr(flat, name)
         setattr(dev, name, torch.from_numpy(arr) if name in host else
@@ -1077,12 +1086,20 @@ class GpuIndex(TableIndex):
         if flat is None:
             return
         block_size = token_processor.block_size
+        t = self.table
+        links = None
+        if self.cfg.event_chain_layout == "linked" and flat.has_parent.any():
+            link, level, n_levels = t.ops.plan_event_links(
+                *(torch.from_numpy(getattr(flat, name)) for name in (
+                    "ehashes", "eh_off", "tok_off", "ev_type", "parents",
+                    "has_parent", "grp_off")), block_size)
+            links = (link, level, int(n_levels))
         route = plan_write_route(flat, block_size,
-                                 self.cfg.event_chain_layout)
+                                 self.cfg.event_chain_layout, links,
+                                 self.cfg.event_link_max_levels)
         up = _event_uploader(self)
         up.begin()
         d = _upload_events(flat, route, up, self.device)
-        t = self.table
         head = (*t._t(), d.tokens, d.tok_off, d.ehashes, d.eh_off, d.parents,
                 d.has_parent, d.ev_type, d.pod_entry)
         tail = (_to_i64(token_processor.config.init_hash()), block_size,
@@ -1096,6 +1113,10 @@ class GpuIndex(TableIndex):
         elif route.op == "gpu_apply_events_split_waves":
             t.ops.gpu_apply_events_split_waves(*head, d.ev_of, d.model_of,
                                                *tail, algo_id)
+        elif route.op == "gpu_apply_events_split_linked":
+            t.ops.gpu_apply_events_split_linked(*head, d.ev_of, d.model_of,
+                                                links[0], links[1], *tail,
+                                                algo_id)
         else:
             t.ops.gpu_apply_events_split_tr(*head, d.ev_of, d.model_of, *tail,
                                             route.max_tokens, algo_id)

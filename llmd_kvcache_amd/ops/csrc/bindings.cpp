@@ -28,6 +28,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("offsets"), py::arg("block_size"));
   m.def("plan_event_waves", &kvidx::plan_event_waves_op, py::arg("tok_off"),
         py::arg("eh_off"), py::arg("ev_type"), py::arg("block_size"));
+  m.def("plan_event_links", &kvidx::plan_event_links_op, py::arg("ehashes"),
+        py::arg("eh_off"), py::arg("tok_off"), py::arg("ev_type"),
+        py::arg("parents"), py::arg("has_parent"), py::arg("grp_off"),
+        py::arg("block_size"));
+  m.def("plan_linked_event_waves", &kvidx::plan_linked_event_waves_op,
+        py::arg("tok_off"), py::arg("eh_off"), py::arg("ev_type"),
+        py::arg("link"), py::arg("level"), py::arg("block_size"));
   m.def("cpu_insert", &kvidx::cpu_insert);
   m.def("cpu_compact", &kvidx::cpu_compact);
   m.def("cpu_evict", &kvidx::cpu_evict);
@@ -164,6 +171,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_size"), py::arg("epoch"), py::arg("shard_id"),
         py::arg("num_shards"), py::arg("algo") = 0,
         py::call_guard<py::gil_scoped_release>());
+  // the same with batch-local parents: the chain entry once per level
+  m.def("gpu_apply_events_split_linked", &kvidx::gpu_apply_events_split_linked,
+        py::arg("keys"), py::arg("meta"), py::arg("stamp"), py::arg("pods"),
+        py::arg("e_keys"), py::arg("e_meta"), py::arg("e_vals"),
+        py::arg("pods_per_key"), py::arg("tokens_flat"), py::arg("tok_off"),
+        py::arg("ehashes"), py::arg("eh_off"), py::arg("parents"),
+        py::arg("has_parent"), py::arg("ev_type"), py::arg("pod_entry"),
+        py::arg("ev_of"), py::arg("model_of"), py::arg("link"),
+        py::arg("level"), py::arg("init_hash_bits"), py::arg("block_size"),
+        py::arg("epoch"), py::arg("shard_id"), py::arg("num_shards"),
+        py::arg("algo") = 0, py::call_guard<py::gil_scoped_release>());
 #else
   m.attr("HAS_HIP") = false;
 #endif

@@ -300,6 +300,37 @@ std::vector<at::Tensor> kvidx::plan_event_waves_op(at::Tensor tok_off,
           p.i32(p.host, p.at_n_chunks(), p.B)};
 }
 
+std::vector<at::Tensor> kvidx::plan_event_links_op(
+    at::Tensor ehashes, at::Tensor eh_off, at::Tensor tok_off,
+    at::Tensor ev_type, at::Tensor parents, at::Tensor has_parent,
+    at::Tensor grp_off, int64_t block_size) {
+  const EventLinks r = plan_event_links(ehashes, eh_off, tok_off, ev_type,
+                                        parents, has_parent, grp_off,
+                                        block_size);
+  return {r.link, r.level, at::full({1}, r.n_levels, at::kLong)};
+}
+
+std::vector<at::Tensor> kvidx::plan_linked_event_waves_op(
+    at::Tensor tok_off, at::Tensor eh_off, at::Tensor ev_type, at::Tensor link,
+    at::Tensor level, int64_t block_size) {
+  TORCH_CHECK(tok_off.numel() >= 1 && eh_off.numel() >= 1,
+              "tok_off and eh_off must hold E + 1 offsets");
+  TORCH_CHECK(level.device().is_cpu() && level.dtype() == at::kInt,
+              "level must be an int32 host tensor");
+  const EventLinks links{
+      level.numel() ? level.max().item<int64_t>() + 1 : 0, link, level};
+  const WavePlan p = plan_linked_event_waves(
+      tok_off, eh_off, ev_type, links, tok_off[-1].item<int64_t>(),
+      eh_off[-1].item<int64_t>(), block_size);
+  return {p.i32(p.host, p.at_perm(), 64 * p.G),
+          p.i32(p.host, p.at_wave_k(), p.G), p.img_off(p.host),
+          p.i32(p.host, p.at_tile_start(), p.G + 1),
+          p.i32(p.host, p.at_h_off(), p.B + 1),
+          p.i32(p.host, p.at_n_chunks(), p.B),
+          p.i32(p.host, p.at_level_wave, p.n_levels + 1),
+          p.i32(p.host, p.at_link, p.B)};
+}
+
 // Tombstone compaction (ROADMAP #9): rehash every live entry of `old`
 // into the freshly-zeroed `nw` bundle (optionally a different power-of-
 // two capacity). Stamps (approximate-LRU epochs) and pod rows are

@@ -2179,8 +2179,33 @@ struct RootEvents {
   }
 };
 
+// RootLinked: RootEvents for bursts whose events chain from each other.
+// The host (plan_event_links) has resolved every batch-local parent to
+// link[e], the index in req_scratch of the parent block's request key, and
+// ordered the launches by level, so a linked lane's root is one load and no
+// lane waits for another workgroup.  link[e] < 0: the engine map, as
+// RootEvents.  A lane without chunks loads nothing.
+// scratch is the kernels' own `out` (req_scratch).  The slot a lane reads
+// here belongs to an event one level below: an EARLIER launch on the same
+// stream wrote it, and this launch, which holds one level's waves only,
+// never writes it.  So nothing reachable through `out` is both written and
+// read in one launch, and the __restrict__ on `out` still holds.
+// A linked root, like an engine-map value, may be below 2^32; the `wide`
+// vote covers it in the same way.
+struct RootLinked {
+  RootEvents ev;
+  const int32_t* __restrict__ link;  // [E]
+  const uint64_t* scratch;           // [n_hashes]
+  DEV uint64_t operator()(int e, int mc) const {
+    if (mc <= 0) return ev.init;
+    const int bi = link[e];
+    return bi >= 0 ? scratch[bi] : ev(e, mc);
+  }
+};
+
 // k_fnv_chain_tr's chunk body over wave g's own image, wave_k[g] trips.
-// One-wave workgroups, block g = wave g: the longest waves are dispatched
+// One-wave workgroups, block g = wave wave0 + g (wave0: 0 except under the
+// per-level launches of the _lk entries): the longest waves are dispatched
 // first.  Lane l is prompt perm[64 g + l]; -1 is a chain of no chunks.
 // out: CSR, chunk c of prompt p at out[h_off[p] + c]; nothing outside
 // [0, total_chunks) is written.
@@ -2189,9 +2214,9 @@ DEV void fnv_chain_waves_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    Root root, uint64_t* __restrict__ out) {
+    int wave0, Root root, uint64_t* __restrict__ out) {
   __shared__ uint64_t stage[64 * CHAIN_STAGE_ROW];
-  const int g = blockIdx.x;
+  const int g = wave0 + (int)blockIdx.x;
   const int wl = threadIdx.x;
   const int p = perm[(int64_t)g * 64 + wl];
   const int pc = max(p, 0);
@@ -2222,7 +2247,7 @@ __global__ void __launch_bounds__(64) k_fnv_chain_waves(
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     uint64_t init, uint64_t* __restrict__ out) {
-  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off,
+  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off, 0,
                            RootInit{init}, out);
 }
 
@@ -2234,8 +2259,21 @@ __global__ void __launch_bounds__(64) k_fnv_chain_waves_ev(
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     RootEvents roots, uint64_t* __restrict__ out) {
-  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off, roots,
-                           out);
+  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off, 0,
+                           roots, out);
+}
+
+// The linked ingest entry: one level's waves [wave0, wave1) of a linked
+// plan, launched level by level (launch_wave_chain).  Grid: wave1 - wave0.
+template <int BS>
+__global__ void __launch_bounds__(64) k_fnv_chain_waves_lk(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int wave0, int wave1, RootLinked roots, uint64_t* __restrict__ out) {
+  if (wave0 + (int)blockIdx.x >= wave1) return;  // the whole one-wave group
+  fnv_chain_waves_body<BS>(img, img_off, perm, wave_k, n_chunks, h_off, wave0,
+                           roots, out);
 }
 
 // k_sha_chain_tr over the per-wave images: wave_k[g] as the loop bound,
@@ -2248,12 +2286,13 @@ DEV void sha_chain_waves_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    int G, Root root, uint64_t* __restrict__ out) {
+    int wave0, int G, Root root, uint64_t* __restrict__ out) {
   constexpr int NT = sha_tr_threads(BS);
   __shared__ uint32_t sha_words[sha_tr_words(BS) * NT];
   const int wl = threadIdx.x & 63;
+  // the launch's waves are [wave0, G), NT / 64 of them per workgroup
   const int g = __builtin_amdgcn_readfirstlane(
-      (int)blockIdx.x * (NT / 64) + (int)(threadIdx.x >> 6));
+      wave0 + (int)blockIdx.x * (NT / 64) + (int)(threadIdx.x >> 6));
   if (g >= G) return;  // a whole wave, and no barrier follows
   const int p = perm[(int64_t)g * 64 + wl];
   const int pc = max(p, 0);
@@ -2283,7 +2322,7 @@ __global__ void k_sha_chain_waves(
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     int G, uint64_t init, uint64_t* __restrict__ out) {
   sha_chain_waves_body<BS, ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
-                                 G, RootInit{init}, out);
+                                 0, G, RootInit{init}, out);
 }
 
 template <int BS, int ALGO>
@@ -2293,7 +2332,19 @@ __global__ void k_sha_chain_waves_ev(
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     int G, RootEvents roots, uint64_t* __restrict__ out) {
   sha_chain_waves_body<BS, ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
-                                 G, roots, out);
+                                 0, G, roots, out);
+}
+
+// One level's waves [wave0, wave1): wave1 is the bound G is above.  Grid:
+// ceil((wave1 - wave0) / (NT / 64)).
+template <int BS, int ALGO>
+__global__ void k_sha_chain_waves_lk(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int wave0, int wave1, RootLinked roots, uint64_t* __restrict__ out) {
+  sha_chain_waves_body<BS, ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+                                 wave0, wave1, roots, out);
 }
 
 // ---------------------------------------------------------------------
@@ -2319,9 +2370,9 @@ DEV void fnv_chain_stream_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    Root root, int block_size, uint64_t* __restrict__ out) {
+    int wave0, Root root, int block_size, uint64_t* __restrict__ out) {
   __shared__ uint64_t stage[64 * CHAIN_STAGE_ROW];
-  const int g = blockIdx.x;
+  const int g = wave0 + (int)blockIdx.x;
   const int wl = threadIdx.x;
   const int p = perm[(int64_t)g * 64 + wl];
   const int pc = max(p, 0);
@@ -2364,7 +2415,7 @@ __global__ void __launch_bounds__(64) k_fnv_chain_stream(
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     uint64_t init, int block_size, uint64_t* __restrict__ out) {
-  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off,
+  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off, 0,
                         RootInit{init}, block_size, out);
 }
 
@@ -2373,8 +2424,19 @@ __global__ void __launch_bounds__(64) k_fnv_chain_stream_ev(
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     RootEvents roots, int block_size, uint64_t* __restrict__ out) {
-  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off, roots,
+  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off, 0, roots,
                         block_size, out);
+}
+
+__global__ void __launch_bounds__(64) k_fnv_chain_stream_lk(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int wave0, int wave1, RootLinked roots, int block_size,
+    uint64_t* __restrict__ out) {
+  if (wave0 + (int)blockIdx.x >= wave1) return;  // the whole one-wave group
+  fnv_chain_stream_body(img, img_off, perm, wave_k, n_chunks, h_off, wave0,
+                        roots, block_size, out);
 }
 
 // SHA-256 over the same payload: chunk_hash_sha256_seg, SHA_SEG_TOKENS
@@ -2390,10 +2452,10 @@ DEV void sha_chain_stream_body(
     const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
-    Root root, int block_size, uint64_t* __restrict__ out) {
+    int wave0, Root root, int block_size, uint64_t* __restrict__ out) {
   constexpr int SEG = SHA_SEG_TOKENS;
   __shared__ uint32_t sha_words[sha_seg_words(SEG) * 64];
-  const int g = blockIdx.x;
+  const int g = wave0 + (int)blockIdx.x;
   const int wl = threadIdx.x;
   const int p = perm[(int64_t)g * 64 + wl];
   const int pc = max(p, 0);
@@ -2430,7 +2492,7 @@ __global__ void __launch_bounds__(64) k_sha_chain_stream(
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     uint64_t init, int block_size, uint64_t* __restrict__ out) {
-  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off, 0,
                               RootInit{init}, block_size, out);
 }
 
@@ -2440,8 +2502,20 @@ __global__ void __launch_bounds__(64) k_sha_chain_stream_ev(
     const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
     const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
     RootEvents roots, int block_size, uint64_t* __restrict__ out) {
-  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off, 0,
                               roots, block_size, out);
+}
+
+template <int ALGO>
+__global__ void __launch_bounds__(64) k_sha_chain_stream_lk(
+    const int32_t* __restrict__ img, const int64_t* __restrict__ img_off,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ wave_k,
+    const int32_t* __restrict__ n_chunks, const int32_t* __restrict__ h_off,
+    int wave0, int wave1, RootLinked roots, int block_size,
+    uint64_t* __restrict__ out) {
+  if (wave0 + (int)blockIdx.x >= wave1) return;  // the whole one-wave group
+  sha_chain_stream_body<ALGO>(img, img_off, perm, wave_k, n_chunks, h_off,
+                              wave0, roots, block_size, out);
 }
 
 template <int ALGO>
@@ -3388,11 +3462,15 @@ std::vector<at::Tensor> kvidx::gpu_topk_flat_tokens(
 
 // Stage and chain over an uploaded wave plan, for the read path's prompts
 // (roots: the batch's one init, uint64_t) and the write path's events
-// (roots: RootEvents): k_stage_ragged_waves, then the templated chain
-// kernel at block sizes 4/8/16/32/64 and the stream kernel at every other,
-// under the entry the roots select.  up: p.host on the device; tok: flat
-// tokens on the device, int64 or int32; out: int64, chunk c of row r at
-// h_off[r] + c.  p.G > 0.  Everything on the current stream.
+// (roots: RootEvents, or RootLinked over a linked plan): one
+// k_stage_ragged_waves, then the templated chain kernel at block sizes
+// 4/8/16/32/64 and the stream kernel at every other, under the entry the
+// roots select.  Under RootLinked the chain entry is launched once per
+// level, with that level's wave range [level_wave[l], level_wave[l + 1]),
+// in level order: the stream orders the launches, the host waits for none,
+// and all levels' images come from the one stage launch.  up: p.host on the
+// device; tok: flat tokens on the device, int64 or int32; out: int64, chunk
+// c of row r at h_off[r] + c.  p.G > 0.  Everything on the current stream.
 namespace kvidx {
 template <typename Roots>
 static void launch_wave_chain(const WavePlan& p, const at::Tensor& up,
@@ -3400,6 +3478,7 @@ static void launch_wave_chain(const WavePlan& p, const at::Tensor& up,
                               int64_t algo, Roots roots,
                               const at::Tensor& out) {
   constexpr bool EV = std::is_same_v<Roots, RootEvents>;
+  constexpr bool LK = std::is_same_v<Roots, RootLinked>;
   const at::Tensor img_off = p.img_off(up);
   const int32_t* w = i32p(up);
   const int32_t* n_chunks = w + p.at_n_chunks();
@@ -3419,26 +3498,50 @@ static void launch_wave_chain(const WavePlan& p, const at::Tensor& up,
     stage(tok.data_ptr<int64_t>());
   else
     stage(tok.data_ptr<int32_t>());
+  // kern over waves [w0, w1), wpg waves per workgroup; with_bound: the
+  // entry takes the range's end behind h_off (the SHA waves kernels); rest:
+  // what follows the roots.  The _lk entries take both ends of the range.
+  auto run = [&](auto kern, auto with_bound, int wpg, auto... rest) {
+    auto launch = [&](int w0, int w1) {
+      const dim3 grid((unsigned)((w1 - w0 + wpg - 1) / wpg)), block(64 * wpg);
+      if constexpr (LK)
+        hipLaunchKernelGGL(kern, grid, block, 0, STREAM, i32p(img),
+                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
+                           h_off, w0, w1, roots, rest...);
+      else if constexpr (decltype(with_bound)::value)
+        hipLaunchKernelGGL(kern, grid, block, 0, STREAM, i32p(img),
+                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
+                           h_off, w1, roots, rest...);
+      else
+        hipLaunchKernelGGL(kern, grid, block, 0, STREAM, i32p(img),
+                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
+                           h_off, roots, rest...);
+    };
+    if constexpr (LK) {
+      const int32_t* level_wave = p.host.data_ptr<int32_t>() + p.at_level_wave;
+      for (int64_t l = 0; l < p.n_levels; ++l)
+        if (level_wave[l + 1] > level_wave[l])  // a level may have no chain
+          launch(level_wave[l], level_wave[l + 1]);
+    } else {
+      launch(0, G);
+    }
+  };
   if (!chain_block_size_templated(block_size)) {
     // one-wave workgroups, block g = wave g, for either hash
     dispatch_algo(algo, [&](auto A) {
       constexpr int AL = decltype(A)::value;
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64), 0, STREAM,
-                           i32p(img), img_off.data_ptr<int64_t>(), perm,
-                           wave_k, n_chunks, h_off, roots, (int)block_size,
-                           u64p(out));
-      };
       if constexpr (AL == ALGO_FNV64A)
-        launch([] {
-          if constexpr (EV) return k_fnv_chain_stream_ev;
+        run([] {
+          if constexpr (LK) return k_fnv_chain_stream_lk;
+          else if constexpr (EV) return k_fnv_chain_stream_ev;
           else return k_fnv_chain_stream;
-        }());
+        }(), std::false_type{}, 1, (int)block_size, u64p(out));
       else
-        launch([] {
-          if constexpr (EV) return k_sha_chain_stream_ev<AL>;
+        run([] {
+          if constexpr (LK) return k_sha_chain_stream_lk<AL>;
+          else if constexpr (EV) return k_sha_chain_stream_ev<AL>;
           else return k_sha_chain_stream<AL>;
-        }());
+        }(), std::false_type{}, 1, (int)block_size, u64p(out));
     });
     return;
   }
@@ -3446,26 +3549,18 @@ static void launch_wave_chain(const WavePlan& p, const at::Tensor& up,
     dispatch_chain_block_size(block_size, [&](auto S) {
       constexpr int AL = decltype(A)::value;
       constexpr int BS = decltype(S)::value;
-      if constexpr (AL == ALGO_FNV64A) {
-        auto kern = [] {
-          if constexpr (EV) return k_fnv_chain_waves_ev<BS>;
+      if constexpr (AL == ALGO_FNV64A)
+        run([] {
+          if constexpr (LK) return k_fnv_chain_waves_lk<BS>;
+          else if constexpr (EV) return k_fnv_chain_waves_ev<BS>;
           else return k_fnv_chain_waves<BS>;
-        }();
-        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64), 0, STREAM,
-                           i32p(img), img_off.data_ptr<int64_t>(), perm,
-                           wave_k, n_chunks, h_off, roots, u64p(out));
-      } else {
-        constexpr int NT = sha_tr_threads(BS);
-        auto kern = [] {
-          if constexpr (EV) return k_sha_chain_waves_ev<BS, AL>;
+        }(), std::false_type{}, 1, u64p(out));
+      else
+        run([] {
+          if constexpr (LK) return k_sha_chain_waves_lk<BS, AL>;
+          else if constexpr (EV) return k_sha_chain_waves_ev<BS, AL>;
           else return k_sha_chain_waves<BS, AL>;
-        }();
-        hipLaunchKernelGGL(kern,
-                           dim3((unsigned)((G + NT / 64 - 1) / (NT / 64))),
-                           dim3(NT), 0, STREAM, i32p(img),
-                           img_off.data_ptr<int64_t>(), perm, wave_k, n_chunks,
-                           h_off, G, roots, u64p(out));
-      }
+        }(), std::true_type{}, sha_tr_threads(BS) / 64, u64p(out));
     });
   });
 }
@@ -3680,6 +3775,68 @@ void kvidx::gpu_apply_events_split_waves(
                       RootEvents{v, u64p(parents), u8p(has_parent),
                                  i32p(model_of), (uint64_t)init_hash_bits},
                       req_scratch);
+  launch_event_inserts(v, ehashes, d_eh_off, ev_of, d_ev_type, d_tok_off,
+                       pod_entry, model_of, block_size, epoch, shard_id,
+                       num_shards, req_scratch);
+}
+
+// Linked wave-tiled phase-split apply: the waves route for bursts WITH
+// batch-local parents (no store+remove conflict; host verified).  link /
+// level: plan_event_links' result, on the host.  plan_linked_event_waves ->
+// the one upload -> stage -> the chain entries level by level (RootLinked)
+// -> k_event_inserts.  No batch map and no k_event_chains: the host plan
+// has done dev_bmap_find's work, and the launch order the waiting.
+void kvidx::gpu_apply_events_split_linked(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor tok_off,
+    at::Tensor ehashes, at::Tensor eh_off, at::Tensor parents,
+    at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
+    at::Tensor ev_of, at::Tensor model_of, at::Tensor link, at::Tensor level,
+    int64_t init_hash_bits, int64_t block_size, int64_t epoch,
+    int64_t shard_id, int64_t num_shards, int64_t algo) {
+  // refused before anything is uploaded or launched
+  TORCH_CHECK(stream_chain_block_size_ok(block_size),
+              "the wave-tiled ingest chain takes block sizes 1..65535");
+  TORCH_CHECK(algo_valid(algo), "unknown chain hash algo id ", algo);
+  auto v = make_table_view(KVIDX_TABLE_ARGS, true);
+  const at::Device dev = keys.device();
+  const auto on_dev = [&](const at::Tensor& t, at::ScalarType ty, int64_t n) {
+    return t.device() == dev && t.dtype() == ty && t.is_contiguous() &&
+           t.numel() == n;
+  };
+  const int64_t E = ev_type.numel();
+  const int64_t n = ehashes.numel();
+  TORCH_CHECK(on_dev(tokens_flat, at::kInt, tokens_flat.numel()),
+              "event tokens must be int32 (uint32 bit pattern) on the "
+              "table's device");
+  TORCH_CHECK(on_dev(ehashes, at::kLong, n) && on_dev(ev_of, at::kInt, n),
+              "ehashes int64 and ev_of int32 must hold one entry per hash "
+              "on the table's device");
+  TORCH_CHECK(on_dev(parents, at::kLong, E) &&
+                  on_dev(has_parent, at::kByte, E) &&
+                  on_dev(pod_entry, at::kInt, E) &&
+                  on_dev(model_of, at::kInt, E),
+              "parents, has_parent, pod_entry and model_of must hold one "
+              "entry per event on the table's device");
+  TORCH_CHECK(level.device().is_cpu() && level.dtype() == at::kInt &&
+                  level.dim() == 1 && level.numel() == E,
+              "level must be an int32 [E] host tensor");
+  const EventLinks links{E ? level.max().item<int64_t>() + 1 : 0, link, level};
+  const WavePlan p = plan_linked_event_waves(
+      tok_off, eh_off, ev_type, links, tokens_flat.numel(), n, block_size);
+  if (E == 0 || n == 0) return;
+  const at::Tensor up = p.host.to(dev);  // the one upload
+  const at::Tensor d_tok_off = p.i32(up, p.at_tok_off(), E + 1);
+  const at::Tensor d_eh_off = p.i32(up, p.at_h_off(), E + 1);
+  const at::Tensor d_ev_type =
+      p.i32(up, p.at_tail(), (E + 3) / 4).view(at::kByte).slice(0, 0, E);
+  auto req_scratch = at::empty({n}, ehashes.options());
+  if (p.G > 0)  // else only removals and dropped stores: the inserts alone
+    launch_wave_chain(
+        p, up, tokens_flat, block_size, algo,
+        RootLinked{RootEvents{v, u64p(parents), u8p(has_parent),
+                              i32p(model_of), (uint64_t)init_hash_bits},
+                   i32p(up) + p.at_link, u64p(req_scratch)},
+        req_scratch);
   launch_event_inserts(v, ehashes, d_eh_off, ev_of, d_ev_type, d_tok_off,
                        pod_entry, model_of, block_size, epoch, shard_id,
                        num_shards, req_scratch);

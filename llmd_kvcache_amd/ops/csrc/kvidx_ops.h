@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "kvidx_common.h"
@@ -56,6 +57,22 @@ std::vector<at::Tensor> plan_event_waves_op(at::Tensor tok_off,
                                             at::Tensor eh_off,
                                             at::Tensor ev_type,
                                             int64_t block_size);
+// The host plans of the linked wave ingest (plan_event_links and
+// plan_linked_event_waves below) as CPU tensors.  plan_event_links_op:
+// {link int32 [E], level int32 [E], n_levels int64 [1]}.
+// plan_linked_event_waves_op: plan_event_waves_op's six, then level_wave
+// int32 [n_levels + 1] and the plan's copy of link.  In every build.
+std::vector<at::Tensor> plan_event_links_op(at::Tensor ehashes,
+                                            at::Tensor eh_off,
+                                            at::Tensor tok_off,
+                                            at::Tensor ev_type,
+                                            at::Tensor parents,
+                                            at::Tensor has_parent,
+                                            at::Tensor grp_off,
+                                            int64_t block_size);
+std::vector<at::Tensor> plan_linked_event_waves_op(
+    at::Tensor tok_off, at::Tensor eh_off, at::Tensor ev_type, at::Tensor link,
+    at::Tensor level, int64_t block_size);
 
 // ---- table ops, CPU (cpu_ops.cpp) ------------------------------------
 void cpu_insert(KVIDX_TABLE_PARAMS, at::Tensor engine_hashes,
@@ -323,6 +340,22 @@ void gpu_apply_events_split_waves(KVIDX_TABLE_PARAMS, at::Tensor tokens_flat,
                                   int64_t block_size, int64_t epoch,
                                   int64_t shard_id, int64_t num_shards,
                                   int64_t algo);
+// The linked wave ingest: the waves op for bursts whose events chain from
+// blocks the same burst stores (no store+remove conflict; host verified).
+// The waves op's arguments plus link / level int32 [E] on the HOST, as
+// plan_event_links returns them.  plan_linked_event_waves -> one upload ->
+// k_stage_ragged_waves -> the linked entry of a wave chain kernel once per
+// level, in level order -> k_event_inserts, on the current stream with no
+// host wait in between; no batch map, no k_event_chains.  Refuses a bad
+// block size or algo and a link that points at or past its own event
+// before any launch.
+void gpu_apply_events_split_linked(
+    KVIDX_TABLE_PARAMS, at::Tensor tokens_flat, at::Tensor tok_off,
+    at::Tensor ehashes, at::Tensor eh_off, at::Tensor parents,
+    at::Tensor has_parent, at::Tensor ev_type, at::Tensor pod_entry,
+    at::Tensor ev_of, at::Tensor model_of, at::Tensor link, at::Tensor level,
+    int64_t init_hash_bits, int64_t block_size, int64_t epoch,
+    int64_t shard_id, int64_t num_shards, int64_t algo);
 #endif
 
 // ---- shared host helpers ---------------------------------------------
@@ -490,6 +523,9 @@ struct WavePlan {
   int64_t B = 0, G = 0, max_k = 0, total_chunks = 0;
   int64_t image_elems = 0, tiles = 0;
   int64_t tail = 0;  // caller's int32 words behind tile_start
+  // the linked event plan only (plan_linked_event_waves): levels, and where
+  // link [B] and level_wave [n_levels + 1] lie in the tail
+  int64_t n_levels = 0, at_link = 0, at_level_wave = 0;
   at::Tensor host;   // int32 [2 (G+1) + 3 B + 2 + 66 G + 1 + tail]
   int64_t at_img_off() const { return 0; }
   int64_t at_n_chunks() const { return 2 * (G + 1); }
@@ -509,12 +545,20 @@ struct WavePlan {
   }
 };
 
-// The wave half of a plan, shared by the prompt plan and the event plan:
+// The wave half of a plan, shared by the prompt plan and the event plans:
 // r holds the lanes' n_chunks and tok_off; h_off_src is the lanes' h_off
 // [B+1], or null for the exclusive prefix sum of n_chunks; tail_words int32
 // words are left to the caller behind tile_start.
+// level: null, or the lanes' levels [B] (plan_event_links).  The lanes with
+// a whole chunk are then ordered by (level ascending, chunks descending,
+// index ascending) and the waves are cut per level: no wave holds two
+// levels, a level's last wave is padded with -1 rows, and level_wave [the
+// levels' count + 1] gets the first wave of each level.  Lanes without a
+// chunk get no row then.
 inline WavePlan plan_waves(const RaggedPlan& r, int64_t block_size,
-                           const int32_t* h_off_src, int64_t tail_words) {
+                           const int32_t* h_off_src, int64_t tail_words,
+                           const int32_t* level = nullptr,
+                           std::vector<int32_t>* level_wave = nullptr) {
   const int32_t* nc = r.host.data_ptr<int32_t>();
   WavePlan p;
   p.B = r.B;
@@ -525,11 +569,43 @@ inline WavePlan plan_waves(const RaggedPlan& r, int64_t block_size,
               "more than 2^31 - 1 chunks in one batch");
   std::vector<int32_t> order(p.B);
   for (int64_t b = 0; b < p.B; ++b) order[b] = (int32_t)b;
-  std::stable_sort(order.begin(), order.end(),
-                   [nc](int32_t a, int32_t b) { return nc[a] > nc[b]; });
+  if (level)
+    std::stable_sort(order.begin(), order.end(),
+                     [nc, level](int32_t a, int32_t b) {
+                       if ((nc[a] > 0) != (nc[b] > 0)) return nc[a] > 0;
+                       if (nc[a] > 0 && level[a] != level[b])
+                         return level[a] < level[b];
+                       return nc[a] > nc[b];
+                     });
+  else
+    std::stable_sort(order.begin(), order.end(),
+                     [nc](int32_t a, int32_t b) { return nc[a] > nc[b]; });
   int64_t live = 0;  // lanes with a whole chunk: they sort first
   while (live < p.B && nc[order[live]] > 0) ++live;
-  p.G = (live + 63) / 64;
+  // rows[64 g + r]: the lane in row r of wave g.  Without levels the last
+  // wave takes chunkless lanes as well, as far as the batch goes.
+  std::vector<int32_t> rows;
+  if (!level) {
+    rows.assign(64 * ((live + 63) / 64), -1);
+    std::copy(order.begin(),
+              order.begin() + std::min<int64_t>(p.B, (int64_t)rows.size()),
+              rows.begin());
+  } else {
+    level_wave->assign(1, 0);
+    for (int64_t i = 0; i < live;) {
+      const int32_t lv = level[order[i]];
+      TORCH_CHECK(lv >= (int64_t)level_wave->size() - 1,
+                  "levels must not be negative");
+      int64_t end = i;
+      while (end < live && level[order[end]] == lv) ++end;
+      level_wave->resize(lv + 1, (int32_t)(rows.size() / 64));  // empty levels
+      rows.insert(rows.end(), order.begin() + i, order.begin() + end);
+      rows.resize((rows.size() + 63) / 64 * 64, -1);
+      level_wave->push_back((int32_t)(rows.size() / 64));
+      i = end;
+    }
+  }
+  p.G = (int64_t)rows.size() / 64;
   p.host = at::empty({p.words()}, at::kInt);
   int32_t* w = p.host.data_ptr<int32_t>();
   int64_t* img_off = reinterpret_cast<int64_t*>(w);
@@ -541,18 +617,17 @@ inline WavePlan plan_waves(const RaggedPlan& r, int64_t block_size,
     h_off[0] = 0;
     for (int64_t b = 0; b < p.B; ++b) h_off[b + 1] = h_off[b] + nc[b];
   }
-  int32_t* perm = w + p.at_perm();
+  std::copy(rows.begin(), rows.end(), w + p.at_perm());
   int32_t* wave_k = w + p.at_wave_k();
   int32_t* tile_start = w + p.at_tile_start();
   img_off[0] = 0;
   tile_start[0] = 0;
   for (int64_t g = 0; g < p.G; ++g) {
-    for (int64_t i = 64 * g; i < 64 * g + 64; ++i)
-      perm[i] = i < p.B ? order[i] : -1;
-    const int64_t rows = (int64_t)nc[order[64 * g]] * block_size;
-    wave_k[g] = nc[order[64 * g]];
-    img_off[g + 1] = img_off[g] + rows * 64;
-    const int64_t tiles = tile_start[g] + (rows + 63) / 64;
+    // a wave's first row is its longest lane
+    wave_k[g] = nc[rows[64 * g]];
+    const int64_t trips = (int64_t)wave_k[g] * block_size;
+    img_off[g + 1] = img_off[g] + trips * 64;
+    const int64_t tiles = tile_start[g] + (trips + 63) / 64;
     TORCH_CHECK(tiles <= INT32_MAX, "too many staging tiles in one batch");
     tile_start[g + 1] = (int32_t)tiles;
   }
@@ -582,10 +657,16 @@ inline WavePlan plan_ragged_waves(const at::Tensor& tokens,
 // The stage kernel reads tokens[tok_off[e] + i] and the chain kernels write
 // out[eh_off[e] + c] unchecked, so both offset arrays are checked here
 // against n_tokens and n_hashes.
+// links: null, or what plan_linked_event_waves adds (below).
+struct EventLinks {
+  int64_t n_levels = 0;
+  at::Tensor link, level;  // int32 [E] each, on the host
+};
 inline WavePlan plan_event_waves(const at::Tensor& tok_off,
                                  const at::Tensor& eh_off,
                                  const at::Tensor& ev_type, int64_t n_tokens,
-                                 int64_t n_hashes, int64_t block_size) {
+                                 int64_t n_hashes, int64_t block_size,
+                                 const EventLinks* links = nullptr) {
   TORCH_CHECK(stream_chain_block_size_ok(block_size),
               "the wave-tiled ingest chain takes block sizes 1..65535");
   const auto host_1d = [](const at::Tensor& t, at::ScalarType ty) {
@@ -619,13 +700,152 @@ inline WavePlan plan_event_waves(const at::Tensor& tok_off,
     r.max_k = std::max<int64_t>(r.max_k, nc[e]);
     r.total_chunks += nc[e];
   }
-  const int64_t tail = (E + 3) / 4;
-  WavePlan p = plan_waves(r, block_size, eo, tail);
+  const int64_t type_words = (E + 3) / 4;
+  WavePlan p;
+  if (!links) {
+    p = plan_waves(r, block_size, eo, type_words);
+  } else {
+    // The chain kernels read scratch[link[e]] unchecked and trust the
+    // launch order, so: a link names a block before its own event's, of a
+    // store with a chain, one level below.
+    TORCH_CHECK(host_1d(links->link, at::kInt) && links->link.numel() == E &&
+                    host_1d(links->level, at::kInt) &&
+                    links->level.numel() == E && links->n_levels >= 0,
+                "link and level must be contiguous int32 [E] host tensors");
+    const int32_t* link = links->link.data_ptr<int32_t>();
+    const int32_t* level = links->level.data_ptr<int32_t>();
+    for (int64_t e = 0; e < E; ++e) {
+      TORCH_CHECK(level[e] >= 0 && level[e] < links->n_levels,
+                  "level[", e, "] is outside the burst's levels");
+      if (link[e] < 0) {
+        TORCH_CHECK(link[e] == -1 && level[e] == 0,
+                    "an event without a link is -1 at level 0");
+        continue;
+      }
+      TORCH_CHECK(link[e] < eo[e], "link[", e,
+                  "] points at or past its own event");
+      const int64_t src = std::upper_bound(eo, eo + E + 1, link[e]) - eo - 1;
+      TORCH_CHECK(nc[src] > 0 && level[e] == level[src] + 1,
+                  "link[", e, "] must name a block of a kept store one "
+                  "level below");
+    }
+    std::vector<int32_t> level_wave;
+    p = plan_waves(r, block_size, eo, type_words + E + links->n_levels + 1,
+                   level, &level_wave);
+    level_wave.resize(links->n_levels + 1, (int32_t)p.G);  // chainless levels
+    p.n_levels = links->n_levels;
+    p.at_link = p.at_tail() + type_words;
+    p.at_level_wave = p.at_link + E;
+    int32_t* w = p.host.data_ptr<int32_t>();
+    std::copy(link, link + E, w + p.at_link);
+    std::copy(level_wave.begin(), level_wave.end(), w + p.at_level_wave);
+  }
   uint8_t* t8 = reinterpret_cast<uint8_t*>(p.host.data_ptr<int32_t>() +
                                            p.at_tail());
-  std::fill(t8 + E, t8 + 4 * tail, (uint8_t)0);
+  std::fill(t8 + E, t8 + 4 * type_words, (uint8_t)0);
   std::copy(ty, ty + E, t8);
   return p;
+}
+
+// Host half of the linked wave ingest (gpu_apply_events_split_linked), part
+// one: which earlier block of its own group each event chains from.  All
+// arguments on the host, as FlatEvents holds them (ehashes / parents int64,
+// has_parent uint8, grp_off int32 [G+1] covering the E events).
+//  - link[e]: the index into ehashes / req_scratch of the block that
+//    k_event_chains takes through dev_bmap_find: the LATEST block bi with
+//    eh_off[first event of e's group] <= bi < eh_off[e] that belongs to a
+//    kept store (ev_type 0, event_chain_len >= 0) and has ehashes[bi] ==
+//    parents[e]; -1 for an event without a parent or without such a block
+//    (a block of another group, of a later event, of a removed or dropped
+//    event: the lane then resolves through the engine map, as RootEvents
+//    does), and for an event that is no kept store itself;
+//  - level[e]: 0 where link[e] < 0, else level[event of link[e]] + 1;
+//  - n_levels: the largest level + 1, 0 for no event.
+// One forward pass with one hash map: hash -> its latest block so far.  The
+// groups follow each other, so an entry below the current group's first
+// block is a stale one of an earlier group and counts as absent.
+inline EventLinks plan_event_links(const at::Tensor& ehashes,
+                                   const at::Tensor& eh_off,
+                                   const at::Tensor& tok_off,
+                                   const at::Tensor& ev_type,
+                                   const at::Tensor& parents,
+                                   const at::Tensor& has_parent,
+                                   const at::Tensor& grp_off,
+                                   int64_t block_size) {
+  TORCH_CHECK(block_size >= 1, "block_size must be positive");
+  const auto host_1d = [](const at::Tensor& t, at::ScalarType ty) {
+    return t.device().is_cpu() && t.dtype() == ty && t.dim() == 1 &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(host_1d(ehashes, at::kLong) && host_1d(parents, at::kLong) &&
+                  host_1d(eh_off, at::kInt) && host_1d(tok_off, at::kInt) &&
+                  host_1d(grp_off, at::kInt) && host_1d(ev_type, at::kByte) &&
+                  host_1d(has_parent, at::kByte),
+              "plan_event_links takes contiguous host tensors: ehashes / "
+              "parents int64, the offsets int32, ev_type / has_parent uint8");
+  const int64_t E = ev_type.numel();
+  const int64_t G = grp_off.numel() - 1;
+  TORCH_CHECK(eh_off.numel() == E + 1 && tok_off.numel() == E + 1 &&
+                  parents.numel() == E && has_parent.numel() == E && G >= 0,
+              "the event arrays must hold E (offsets: E + 1) entries");
+  const uint64_t* eh = u64p(ehashes);
+  const uint64_t* par = u64p(parents);
+  const int32_t* eo = eh_off.data_ptr<int32_t>();
+  const int32_t* to = tok_off.data_ptr<int32_t>();
+  const int32_t* go = grp_off.data_ptr<int32_t>();
+  const uint8_t* ty = ev_type.data_ptr<uint8_t>();
+  const uint8_t* hp = has_parent.data_ptr<uint8_t>();
+  TORCH_CHECK(eo[0] >= 0 && eo[E] <= ehashes.numel(),
+              "eh_off reaches outside the engine hashes");
+  TORCH_CHECK(go[0] == 0 && go[G] == E, "grp_off must cover the events");
+  EventLinks r;
+  r.link = at::empty({E}, at::kInt);
+  r.level = at::empty({E}, at::kInt);
+  int32_t* link = r.link.data_ptr<int32_t>();
+  int32_t* level = r.level.data_ptr<int32_t>();
+  struct Block { int32_t index, event; };
+  std::unordered_map<uint64_t, Block> latest;
+  latest.reserve((size_t)ehashes.numel());
+  for (int64_t g = 0; g < G; ++g) {
+    TORCH_CHECK(go[g + 1] >= go[g], "grp_off must not decrease");
+    const int32_t first_block = eo[go[g]];
+    for (int64_t e = go[g]; e < go[g + 1]; ++e) {
+      TORCH_CHECK(to[e + 1] >= to[e] && eo[e + 1] >= eo[e],
+                  "event offsets must not decrease");
+      link[e] = -1;
+      level[e] = 0;
+      if (ty[e] != 0 || (to[e + 1] - to[e]) / block_size != eo[e + 1] - eo[e])
+        continue;  // no kept store: chains nothing, is nobody's parent
+      if (hp[e]) {
+        const auto it = latest.find(par[e]);
+        if (it != latest.end() && it->second.index >= first_block) {
+          link[e] = it->second.index;
+          level[e] = level[it->second.event] + 1;
+        }
+      }
+      for (int32_t bi = eo[e]; bi < eo[e + 1]; ++bi)
+        latest[eh[bi]] = Block{bi, (int32_t)e};
+      r.n_levels = std::max<int64_t>(r.n_levels, level[e] + 1);
+    }
+  }
+  if (E > 0) r.n_levels = std::max<int64_t>(r.n_levels, 1);
+  return r;
+}
+
+// Part two: plan_event_waves with the lanes ordered by (level ascending,
+// chunks descending, index ascending) and the waves cut per level
+// (plan_waves), so that the chain kernels can run level by level over one
+// set of images: wave g of level l is level_wave[l] <= g < level_wave[l+1].
+// The tail behind tile_start is then [ev_type (E + 3) / 4 words | link (E) |
+// level_wave (n_levels + 1)] - still one upload.  h_off stays eh_off.
+inline WavePlan plan_linked_event_waves(const at::Tensor& tok_off,
+                                        const at::Tensor& eh_off,
+                                        const at::Tensor& ev_type,
+                                        const EventLinks& links,
+                                        int64_t n_tokens, int64_t n_hashes,
+                                        int64_t block_size) {
+  return plan_event_waves(tok_off, eh_off, ev_type, n_tokens, n_hashes,
+                          block_size, &links);
 }
 
 // Runs f(std::integral_constant<int, ALGO>) for a native chain algo id
